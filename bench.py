@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: BPR triplets/s of a LightGCN training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the line; `ms_per_step` is the wall time of one timed
+step.  Everything else this file measures -- the per-kernel roofline, the measured-ceiling probes, the all-rows and
+big-batch variants, the HIP-graph replay, the C3 / C4 legs, the collective probe of the sharded path and the CPU
+baseline -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step handed its caller (see
+dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "C2"): LightGCN, 3 layers, dim 64, synthetic
 1M users x 1M items x 50M edges (N = 2M nodes, nnz = 100M), bi_norm adjacency, BPR softplus loss,
@@ -21,7 +27,7 @@ layers that need every row, the top layer in push form on the batch rows, flagge
 gathers whole 128-byte rows): every rank holds D/N columns of every row plus the whole CSR; only row
 norms, row dot products and the B triplet scores are all-reduced.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, the fused forward layer on all rows
+Prints ONE JSON line (rank 0).  With --full, `roofline` is for the dominant kernel, the fused forward layer on all rows
 (`spmm_rows_kernel<16, NORM_ACC>`, run without the layer-mean accumulator: the training step forms the mean on the
 batch rows): algorithmic bytes per launch ((8+4D) per stored entry + (8+4D) per row + 4 per row for the
 norm) divided by its mean duration from HIP events recorded on the launch stream inside the timed region.
@@ -29,7 +35,7 @@ norm) divided by its mean duration from HIP events recorded on the launch stream
 random 256-byte-row gathers from 256 MB / 512 MB / 4 GB tables), `frac_of_gather_ceiling` prices the kernel against them.
 `cpu_baseline` times the CPU oracle (PyTorch CPU restatement of the reference path, checked against
 the reference in tests/golden) on the same graph and batch size, on the box's host cores: 1 warm-up + 3 timed steps.
-At N = 1 the headline run also carries `extra.configs.C3` (NGCF, same graph) and `.C4` (TGCN, 1 M / 1 M / 2 M nodes; with
+At N = 1 the headline run with --full also carries `extra.configs.C3` (NGCF, same graph) and `.C4` (TGCN, 1 M / 1 M / 2 M nodes; with
 the shader clock measured under its fused kernel) as short legs in the same process, and `extra.hip_graph_replay` (the same
 C2 step as one captured HIP graph).  `--model ngcf|tgcn|dgcf|...` run those models on their own.
 NOTE: the multi-rank path has been verified over gloo and in an RCCL group of one; it has never run over xGMI.
@@ -57,6 +63,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (nodes and edges) for quick runs")
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every figure besides the headline: roofline and per-kernel times, measured ceilings, "
+                         "all-rows / big-batch / HIP-graph variants, the C3 and C4 legs, collective probe, CPU baseline "
+                         "(the --no-* and --big-batch / --cpu-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the loss and the trained parameters of the last step as DIR/<name>.npy")
     ap.add_argument("--big-batch", type=int, default=786432, help="also report triplets/s at this batch (0 = skip)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--cpu-steps", type=int, default=3,
@@ -98,6 +110,31 @@ def parse():
 
 def spmm_bytes(nnz, n_rows, D, epilogue_row_bytes):
     return nnz * (8 + 4 * D) + n_rows * (8 + 4 * D) + n_rows * epilogue_row_bytes
+
+
+DUMP_LIMIT_BYTES = 48 << 20        # all files of one --dump-outputs together
+DUMP_WHOLE_ELEMS = 1 << 20         # parameters up to this size are written whole, larger ones as a sample of rows
+
+
+def dump_outputs(out_dir, loss, named_params):
+    """--dump-outputs: what the timed step returned to its caller after the last timed step.  `loss.npy` = the loss parts
+    (float64); `<parameter name>.npy` = every trained parameter after the optimizer step (float32).  A parameter of more than
+    DUMP_WHOLE_ELEMS elements (the node tables) is written as a fixed sample of its rows: the first k entries of
+    torch.randperm(rows) from a CPU generator seeded with 0, sorted -- the same rows in every run of the same shape -- with k
+    chosen so that all files stay within DUMP_LIMIT_BYTES.  On a sharded run rank 0 writes its own shard."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([float(x.detach()) for x in loss], dtype=np.float64))
+    params = [(name, p.detach()) for name, p in named_params]
+    small = sum(p.numel() * 4 for _, p in params if p.numel() <= DUMP_WHOLE_ELEMS)
+    big = [p for _, p in params if p.numel() > DUMP_WHOLE_ELEMS]
+    share = (DUMP_LIMIT_BYTES - small) // max(1, len(big))
+    for name, p in params:
+        if p.numel() > DUMP_WHOLE_ELEMS:
+            k = min(p.shape[0], max(1, share // (p[0].numel() * 4)))
+            rows = torch.randperm(p.shape[0], generator=torch.Generator().manual_seed(0))[:k].sort().values
+            p = p[rows.to(p.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), p.float().cpu().numpy())
 
 
 def kernel_source_sha16():
@@ -283,83 +320,85 @@ def bench_tgcn(args, ceilings=None):
     import gc
     gc.collect()
     gc.freeze()                   # (see main(): a full collection inside the timed region is a ~30 ms host stall)
-    TG.timing = {}
+    TG.timing = {} if args.full else None
     torch.cuda.synchronize()
     t = time.perf_counter()
     last = run(batches[W:], model.loss)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t
-    ms = {kk: [a.elapsed_time(b) for a, b in v] for kk, v in TG.timing.items()}
-    # roofline kernel on ALL rows: the training step runs every layer only on the rows the batch's loss depends on
-    # (TGCN._forward_rows), so its launches vary in size; one full forward pass gives the kernel's all-rows duration
-    TG.timing = {}
-    with torch.no_grad():
-        model.forward()
-    torch.cuda.synchronize()
-    full_ms = {kk: [a.elapsed_time(b) for a, b in v] for kk, v in TG.timing.items()}
-    TG.timing = None
-    # transtag phase, one step, for the record
-    tt = T.TransTag_training_data(ds, config=cfg, seed=1)
-    tb = tt.all_train_data[:cfg["transtag_batch"]]
-    run([tb], model.transtag_loss)
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    run([tt.all_train_data[512:1024]], model.transtag_loss)
-    torch.cuda.synchronize()
-    t_tt = time.perf_counter() - t
-    n_pairs = sum(int(p[0].shape[0]) for p in model.nbr)          # (node, relation) pairs per layer
-    A = cfg["dim_atten"]
-    alg = n_pairs / 6 * k * (4 * D + 4 * A + 8) + n_pairs / 6 * (4 * D + 4 * A + 4 * k)   # mean per launch (one relation)
-    fwd = full_ms.get("attn_fwd", [])
-    roof = None
-    if fwd:
-        m = sum(fwd) / len(fwd)
-        ach = alg / (m * 1e-3) / 1e9
-        roof = {"bound": "hbm", "kernel": "tgcn_attn_fwd_kernel<32> (mean over the six relations)", "achieved": ach,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                "traffic_source": "none: rocprofv3 averages a kernel over all its launches, and this step launches the kernel "
-                                  "on row subsets of varying size; per-kernel means of the step are in profiles/r02_pmc_c4_tgcn.csv",
-                "algorithmic_bytes_per_launch": alg, "mean_launch_ms": m, "launches_timed": len(fwd),
-                "measured_on": "one full forward pass over all rows, after the timed steps",
-                "all_rows_kernels_ms": {kk: sum(v) / len(v) for kk, v in full_ms.items() if kk != "attn_fwd"},
-                "step_kernels_ms_per_step": {kk: sum(v) / K for kk, v in ms.items()}}
-    n_nodes = nu + ni + nt
-    # the other bounding roofline of C4: the fusion product of the fused dense kernel on the MFMA pipe
-    fuse_all = full_ms.get("fuse_fwd", [])
-    roof_mfma = None
-    if fuse_all:
-        tf = L * 2 * n_nodes * (32 * D + 48) * D / 1e12 / (sum(fuse_all) * 1e-3)
-        roof_mfma = {"bound": "mfma", "kernel": "tgcn_fuse_fwd kernel (type attention + convolutions + fusion layer), all rows, "
-                                                "flops of the fusion product 2 n (32 D + 48) D only",
-                     "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
-                     "traffic": None, "ms_all_rows_per_layer": sum(fuse_all) / L}
-    if roof_mfma is not None:
-        # the clock the kernel actually runs at: the 157 TFLOP/s peak is quoted at 2.4 GHz, the chip lowers its clock under
-        # the fp32 matrix load.  A one-wave sampler (tagrec_probe_clock) on a second stream, launched first, spins through
-        # one forward launch on 1 M random rows.
-        try:
-            from tagrec_amd import _lib
-            g_ = torch.Generator(device=dev).manual_seed(0)
-            rnd = lambda *sh: torch.randn(*sh, device=dev, generator=g_) * 0.1
-            tt3 = [rnd(1_000_000, D) for _ in range(3)]
-            lp = TS_dense_views([p_.detach() for p_ in TS_layer_params(model.layer["0"])[12:]])
-            res = torch.zeros(2, dtype=torch.int64, device=dev)
-            side = torch.cuda.Stream()
-            torch.cuda.synchronize()
-            with torch.cuda.stream(side):
-                _lib.check(_lib.load().tagrec_probe_clock(6000, _lib.ptr(res), _lib.c_void_p(side.cuda_stream)), "probe_clock")
-            with torch.no_grad():
-                TG._FusedDense.apply(*tt3, *lp, 0)
-            torch.cuda.synchronize()
-            cyc, ticks = res.tolist()
-            mhz = cyc / ticks * 100.0
-            roof_mfma["shader_clock_mhz_under_kernel"] = round(mhz)
-            roof_mfma["frac_at_measured_clock"] = tf / (MFMA_F32_PEAK_TFLOPS * mhz / 2400.0)
-            del tt3
-        except Exception as e:                                   # a diagnostic: never fails the bench line
-            roof_mfma["shader_clock_mhz_under_kernel"] = f"not measured: {e}"
-    if roof is not None and ceilings:
-        roof["measured_ceilings"] = ceilings
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, model.named_parameters())
+    roof = roof_mfma = None
+    if args.full:
+        ms = {kk: [a.elapsed_time(b) for a, b in v] for kk, v in TG.timing.items()}
+        # roofline kernel on ALL rows: the training step runs every layer only on the rows the batch's loss depends on
+        # (TGCN._forward_rows), so its launches vary in size; one full forward pass gives the kernel's all-rows duration
+        TG.timing = {}
+        with torch.no_grad():
+            model.forward()
+        torch.cuda.synchronize()
+        full_ms = {kk: [a.elapsed_time(b) for a, b in v] for kk, v in TG.timing.items()}
+        TG.timing = None
+        # transtag phase, one step, for the record
+        tt = T.TransTag_training_data(ds, config=cfg, seed=1)
+        tb = tt.all_train_data[:cfg["transtag_batch"]]
+        run([tb], model.transtag_loss)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        run([tt.all_train_data[512:1024]], model.transtag_loss)
+        torch.cuda.synchronize()
+        t_tt = time.perf_counter() - t
+        n_pairs = sum(int(p[0].shape[0]) for p in model.nbr)          # (node, relation) pairs per layer
+        A = cfg["dim_atten"]
+        alg = n_pairs / 6 * k * (4 * D + 4 * A + 8) + n_pairs / 6 * (4 * D + 4 * A + 4 * k)   # mean per launch (one relation)
+        fwd = full_ms.get("attn_fwd", [])
+        if fwd:
+            m = sum(fwd) / len(fwd)
+            ach = alg / (m * 1e-3) / 1e9
+            roof = {"bound": "hbm", "kernel": "tgcn_attn_fwd_kernel<32> (mean over the six relations)", "achieved": ach,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                    "traffic_source": "none: rocprofv3 averages a kernel over all its launches, and this step launches the kernel "
+                                      "on row subsets of varying size; per-kernel means of the step are in profiles/r02_pmc_c4_tgcn.csv",
+                    "algorithmic_bytes_per_launch": alg, "mean_launch_ms": m, "launches_timed": len(fwd),
+                    "measured_on": "one full forward pass over all rows, after the timed steps",
+                    "all_rows_kernels_ms": {kk: sum(v) / len(v) for kk, v in full_ms.items() if kk != "attn_fwd"},
+                    "step_kernels_ms_per_step": {kk: sum(v) / K for kk, v in ms.items()}}
+        n_nodes = nu + ni + nt
+        # the other bounding roofline of C4: the fusion product of the fused dense kernel on the MFMA pipe
+        fuse_all = full_ms.get("fuse_fwd", [])
+        if fuse_all:
+            tf = L * 2 * n_nodes * (32 * D + 48) * D / 1e12 / (sum(fuse_all) * 1e-3)
+            roof_mfma = {"bound": "mfma", "kernel": "tgcn_fuse_fwd kernel (type attention + convolutions + fusion layer), all rows, "
+                                                    "flops of the fusion product 2 n (32 D + 48) D only",
+                         "achieved": tf, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_F32_PEAK_TFLOPS,
+                         "traffic": None, "ms_all_rows_per_layer": sum(fuse_all) / L}
+        if roof_mfma is not None:
+            # the clock the kernel actually runs at: the 157 TFLOP/s peak is quoted at 2.4 GHz, the chip lowers its clock under
+            # the fp32 matrix load.  A one-wave sampler (tagrec_probe_clock) on a second stream, launched first, spins through
+            # one forward launch on 1 M random rows.
+            try:
+                from tagrec_amd import _lib
+                g_ = torch.Generator(device=dev).manual_seed(0)
+                rnd = lambda *sh: torch.randn(*sh, device=dev, generator=g_) * 0.1
+                tt3 = [rnd(1_000_000, D) for _ in range(3)]
+                lp = TS_dense_views([p_.detach() for p_ in TS_layer_params(model.layer["0"])[12:]])
+                res = torch.zeros(2, dtype=torch.int64, device=dev)
+                side = torch.cuda.Stream()
+                torch.cuda.synchronize()
+                with torch.cuda.stream(side):
+                    _lib.check(_lib.load().tagrec_probe_clock(6000, _lib.ptr(res), _lib.c_void_p(side.cuda_stream)), "probe_clock")
+                with torch.no_grad():
+                    TG._FusedDense.apply(*tt3, *lp, 0)
+                torch.cuda.synchronize()
+                cyc, ticks = res.tolist()
+                mhz = cyc / ticks * 100.0
+                roof_mfma["shader_clock_mhz_under_kernel"] = round(mhz)
+                roof_mfma["frac_at_measured_clock"] = tf / (MFMA_F32_PEAK_TFLOPS * mhz / 2400.0)
+                del tt3
+            except Exception as e:                                   # a diagnostic: never fails the bench line
+                roof_mfma["shader_clock_mhz_under_kernel"] = f"not measured: {e}"
+        if roof is not None and ceilings:
+            roof["measured_ceilings"] = ceilings
     out = {"metric": f"BPR triplets/sec, TGCN {L}-layer dim{D}, tripartite {nu}/{ni}/{nt} nodes, k={k}",
            "value": K * B / dt, "unit": "triplets/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -369,11 +408,13 @@ def bench_tgcn(args, ceilings=None):
            "cpu_baseline": "not run (the reference cannot materialise this size: 4 M x (32 D + 48) floats "
                            "of convolution output per layer)",
            "extra": {"build_s": round(t_build, 1), "last_loss": [float(x.detach()) for x in last],
-                     "transtag_step_ms": t_tt * 1e3,
-                     "attention_ms_per_step": sum(sum(v) for kk, v in ms.items() if kk.startswith("attn")) / K,
+                     **({"transtag_step_ms": t_tt * 1e3,
+                         "attention_ms_per_step": sum(sum(v) for kk, v in ms.items() if kk.startswith("attn")) / K}
+                        if args.full else {}),
                      "pruned_forward": bool(model.prune_forward),
                      "fused_adam": bool(not args.no_fused_adam),
-                     "fused_dense_ms_per_step": sum(sum(ms.get(kk, [])) for kk in ("fuse_fwd", "fuse_bwd", "fuse_wf")) / K,
+                     **({"fused_dense_ms_per_step": sum(sum(ms.get(kk, [])) for kk in ("fuse_fwd", "fuse_bwd", "fuse_wf")) / K}
+                        if args.full else {}),
                      "note": "the step is one hand-derived autograd node (tgcn_step.py): fused MFMA dense block (csrc/tgcn_fuse.hip: fwd, "
                              "bwd-data, bwd-Wf; the three node types of a layer in one launch), neighbour attention (csrc/tgcn.hip) with the "
                              "backward pulled over on-the-spot inverted tables (csrc/spmm.hip attn_pull_*), projections on csrc/proj.hip; "
@@ -576,21 +617,24 @@ def run_table_model(args, dev, rank, world, sharded, ceilings=None, ds=None, lig
     gc.collect()
     gc.freeze()
     row_sharded = sharded and parallel == "row"
-    probe = collective_probe((model.part.rc, D), dev, world, rank) if (row_sharded and world > 1) else None
+    probe = collective_probe((model.part.rc, D), dev, world, rank) if (args.full and row_sharded and world > 1) else None
     # per-kernel HIP events on the launch stream; a row shard is walked in row blocks, one handle (and event list) each
     timed_graphs = model.graph_chunks if row_sharded else [timed_graph]
-    for g_ in timed_graphs:
-        g_.timing = {}
+    if args.full:
+        for g_ in timed_graphs:
+            g_.timing = {}
     if sharded:
-        model.timing, model.comm_bytes = {}, 0
+        model.timing, model.comm_bytes = ({} if args.full else None), 0
     dt, last = timed(batches[W:])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, model.named_parameters())
     per_block = [g_.timing_ms() for g_ in timed_graphs]
     kernel_ms = {k: [sum(v) for v in zip(*[pb.get(k, []) for pb in per_block])] for k in per_block[0]}
     for g_ in timed_graphs:
         g_.timing = None
     loss_val = [float(x) for x in last]
     comm = None
-    if sharded:
+    if sharded and args.full:
         waits = model.timing_ms()
         model.timing = None
         comm = {"world_size_seen_by_torch_distributed": dist.get_world_size(), "backend": dist.get_backend(),
@@ -608,6 +652,7 @@ def run_table_model(args, dev, rank, world, sharded, ceilings=None, ds=None, lig
              "edge_layers_per_s": nnz * L * 2 * K / dt}
     if comm is not None:
         extra["collectives"] = comm
+    light = light or not args.full              # the variants below are --full figures
     if args.model == "lightgcn" and not sharded and not light and getattr(model, "restrict_forward", False):
         # the same step with every forward layer computed on ALL rows (the timed step above computes the top two
         # layers only on the rows the batch's loss depends on -- same loss and gradients)
@@ -688,7 +733,7 @@ def run_table_model(args, dev, rank, world, sharded, ceilings=None, ds=None, lig
     epi_name = "SS" if dom == "spmm_ss" else ("NORM_ACC" if args.model == "lightgcn" else "NONE")
     epi_id = {"NONE": 0, "NORM_ACC": 1, "SS": 4}[epi_name]
     prof_kname = f"spmm_rows_kernel<{Dl // 4}, {epi_id}, false>"
-    if world == 1 and args.scale == 1.0 and not routed:
+    if args.full and world == 1 and args.scale == 1.0 and not routed:
         traffic, traffic_source = committed_traffic(args.model, D, prof_kname)
     if fwd:
         ms = sum(fwd) / len(fwd)
@@ -754,7 +799,7 @@ def run_table_model(args, dev, rank, world, sharded, ceilings=None, ds=None, lig
                           "step": "loss -> backward -> Adam on one batch; same loss and gradients as the all-rows step: rows "
                                   "of the top two forward layers that the batch's loss does not read are not computed, "
                                   "backward products do not fetch operand rows that are exactly zero "
-                                  "(extra.ms_per_step_all_rows_forward = every forward layer on all rows)"
+                                  "(with --full, extra.ms_per_step_all_rows_forward = every forward layer on all rows)"
                                   + ("; the table's Adam update (torch's arithmetic, bit-identical) runs in the epilogue of the "
                                      "last backward product instead of a separate launch (--no-fused-adam separates them)"
                                      if (not args.no_fused_adam and getattr(model, "_fused_opt", None) is not None) else "")},
@@ -819,7 +864,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
     # measured ceilings of this box (rank 0's GPU; every rank runs them so that the ranks stay in step)
-    ceilings = None if args.no_probes else probe_ceilings(dev)
+    ceilings = probe_ceilings(dev) if (args.full and not args.no_probes) else None
     if args.model == "tgcn":
         print(json.dumps(bench_tgcn(args, ceilings)))
         return
@@ -832,7 +877,8 @@ def main():
             dist.broadcast(t_, 0)
             picked = "feature" if int(t_) else "row"
         other = "row" if picked == "feature" else "feature"
-        o_other, _, ds = run_table_model(_leg_args(args, parallel=other), dev, rank, world, sharded, ceilings, ds=ds, light=True)
+        o_other, _, ds = run_table_model(_leg_args(args, parallel=other, dump_outputs=None), dev, rank, world, sharded, ceilings,
+                                         ds=ds, light=True)
         out = o_auto
         if rank == 0:
             out["extra"]["partitions"] = {picked: {"ms_per_step": o_auto["ms_per_step"], "value": o_auto["value"]},
@@ -843,27 +889,28 @@ def main():
         out, cpu_inputs, ds = run_table_model(args, dev, rank, world, sharded, ceilings)
     if rank == 0:
         headline = (args.model == "lightgcn" and not sharded and args.scale == 1.0 and args.dim == 64 and args.layers == 3)
-        if headline and not args.no_extra_configs:
+        if headline and args.full and not args.no_extra_configs:
             # the other single-GPU configurations of BASELINE.json, short legs in the same process so that the driver's
             # clock covers them: C3 = NGCF on the same graph, C4 = TGCN on the tripartite graph
             legs = {}
             print("[bench] extra.configs: C3 NGCF leg ...", file=sys.stderr, flush=True)
-            c3, _, _ = run_table_model(_leg_args(args, model="ngcf", steps=10, warmup=3, big_batch=0), dev, 0, 1, False, ceilings,
-                                       ds=ds, light=True)
+            c3, _, _ = run_table_model(_leg_args(args, model="ngcf", steps=10, warmup=3, big_batch=0, dump_outputs=None), dev, 0, 1,
+                                       False, ceilings, ds=ds, light=True)
             legs["C3"] = _compact(c3)
             del ds
             torch.cuda.empty_cache()
             print("[bench] extra.configs: C4 TGCN leg ...", file=sys.stderr, flush=True)
-            legs["C4"] = _compact(bench_tgcn(_leg_args(args, model="tgcn", steps=8, warmup=3, dim=128), ceilings))
+            legs["C4"] = _compact(bench_tgcn(_leg_args(args, model="tgcn", steps=8, warmup=3, dim=128, dump_outputs=None), ceilings))
             out["extra"]["configs"] = legs
         ds = None
         torch.cuda.empty_cache()
-        if not args.no_cpu and cpu_inputs is not None:
+        if args.full and not args.no_cpu and cpu_inputs is not None:
             out["cpu_baseline"] = cpu_baseline(args, args.model, *cpu_inputs)
         else:
             out["cpu_baseline"] = ("not run (--no-cpu)" if args.no_cpu else
                                    "not run (timed on rank 0 of the 1-GPU configuration only)" if world > 1 or sharded else
-                                   "not run (no CPU oracle leg for this model in bench.py)")
+                                   "not run (no CPU oracle leg for this model in bench.py)" if cpu_inputs is None else
+                                   "not run (part of --full)")
         print(json.dumps(out))
     if sharded:
         dist.barrier()

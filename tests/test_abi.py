@@ -221,3 +221,28 @@ def test_bench_refuses_more_ranks_than_gpus_without_touching_the_gpu():
     assert r.returncode == 2, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and "one rank per GPU" in line["error"]
+
+
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """bench.dump_outputs (behind --dump-outputs): loss parts in float64, small parameters whole, a large table as the same
+    seeded row sample on every call, everything within the 64 MB bound."""
+    import bench
+    g = torch.Generator().manual_seed(1)
+    m = torch.nn.Module()
+    m.table = torch.nn.Parameter(torch.randn(1_500_000, 64, generator=g))
+    m.W = torch.nn.Parameter(torch.randn(64, 64, generator=g))
+    loss = [torch.tensor(0.6931, requires_grad=True), torch.tensor(0.0)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss, m.named_parameters())
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(f.name for f in a.iterdir()) == ["W.npy", "loss.npy", "table.npy"]
+    assert sum(f.stat().st_size for f in a.iterdir()) <= 64 << 20
+    got = {f.name: np.load(f) for f in a.iterdir()}
+    assert got["loss.npy"].dtype == np.float64 and got["loss.npy"][0] == np.float32(0.6931)
+    assert np.array_equal(got["W.npy"], m.W.detach().numpy())
+    t = got["table.npy"]
+    assert t.dtype == np.float32 and 100_000 < t.shape[0] < 1_500_000 and t.shape[1] == 64
+    rows = torch.randperm(1_500_000, generator=torch.Generator().manual_seed(0))[:t.shape[0]].sort().values
+    assert np.array_equal(t, m.table.detach()[rows].numpy())
+    for f in a.iterdir():
+        assert np.array_equal(np.load(f), np.load(b / f.name))

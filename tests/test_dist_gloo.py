@@ -5,7 +5,6 @@ checks the partitioning, the all-gather / all-reduce plumbing, the batch-row exc
 gradient scatter of tagrec_amd/dist.py against the single-process oracle.  The HIP kernels
 themselves are checked in the -m gpu tests."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -216,13 +215,15 @@ class CpuOps:
         return torch.stack([(u * p).sum(1), (u * n).sum(1), reg], dim=1).contiguous()
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def _rendezvous(tmp_path):
+    """init_method of one group: a FileStore in a fresh directory of the test.  (A port picked free and released before
+    rank 0 listens on it lets a rank's retried connect() land on that very port -- a TCP self-connect -- or another
+    process take it.)"""
+    import tempfile
+    return "file://" + os.path.join(tempfile.mkdtemp(dir=tmp_path), "store")
 
 
-def _feature_worker(rank, world, port, out_dir, n_layer, restrict):
+def _feature_worker(rank, world, init, out_dir, n_layer, restrict):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -230,7 +231,7 @@ def _feature_worker(rank, world, port, out_dir, n_layer, restrict):
     from tagrec_amd import dist as TD
     from oracle import adj as oadj
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("lightgcn_toy")
         csr = oadj.normalise(oadj.block_adjacency(*blocks_from_fixture(fx, 1)), "bi_norm")
@@ -269,8 +270,8 @@ def _feature_worker(rank, world, port, out_dir, n_layer, restrict):
 def test_feature_sharded_lightgcn_matches_single_process(tmp_path, golden, world, n_layer, restrict):
     """Column-sharded tables: per-column products; all-rows step = all-reduced row norms / row dots / triplet scores over
     [L, N]; restricted step = the same quantities on the 3 B batch rows only."""
-    port = _free_port()
-    mp.spawn(_feature_worker, args=(world, port, str(tmp_path), n_layer, restrict), nprocs=world, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_feature_worker, args=(world, init, str(tmp_path), n_layer, restrict), nprocs=world, join=True)
     got = np.load(tmp_path / "feat.npz")
     fx = golden("lightgcn_toy")
     if n_layer == 2:
@@ -310,12 +311,12 @@ def _row_model(rank, world, fx, n_layer, n_chunks, restrict, norm="bi_norm", all
     return m, csr, full
 
 
-def _worker(rank, world, port, out_dir, n_layer, n_chunks, restrict, all_gather="collective", tag="row"):
+def _worker(rank, world, init, out_dir, n_layer, n_chunks, restrict, all_gather="collective", tag="row"):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("lightgcn_toy")
         m, csr, full = _row_model(rank, world, fx, n_layer, n_chunks, restrict, all_gather=all_gather)
@@ -366,8 +367,8 @@ def _single_process(fx, n_layer):
     (2, 2, 1, False), (3, 2, 2, False), (2, 2, 1, True), (3, 2, 3, True),
     (2, 3, 2, True), (2, 1, 1, True), (2, 3, 1, False), (4, 3, 2, True)])
 def test_sharded_lightgcn_matches_single_process(tmp_path, golden, world, n_layer, n_chunks, restrict):
-    port = _free_port()
-    mp.spawn(_worker, args=(world, port, str(tmp_path), n_layer, n_chunks, restrict), nprocs=world, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_worker, args=(world, init, str(tmp_path), n_layer, n_chunks, restrict), nprocs=world, join=True)
     got = np.load(tmp_path / "row.npz")
     fx = golden("lightgcn_toy")
     if n_layer == 2:                                      # the depth the reference fixture was captured at
@@ -394,19 +395,19 @@ def test_direct_all_gather_is_bit_identical_to_the_collective(tmp_path, world, n
     uneven shards, one and several row blocks, restricted and all-rows steps."""
     res = {}
     for mode in ("collective", "direct"):
-        port = _free_port()
-        mp.spawn(_worker, args=(world, port, str(tmp_path), n_layer, n_chunks, restrict, mode, mode), nprocs=world, join=True)
+        init = _rendezvous(tmp_path)
+        mp.spawn(_worker, args=(world, init, str(tmp_path), n_layer, n_chunks, restrict, mode, mode), nprocs=world, join=True)
         res[mode] = dict(np.load(tmp_path / f"{mode}.npz"))
     for k in res["collective"]:
         assert np.array_equal(res["collective"][k], res["direct"][k]), k
 
 
-def _asym_worker(rank, world, port, out_dir):
+def _asym_worker(rank, world, init, out_dir):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from tagrec_amd._lib import TagrecError
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("lightgcn_toy")
         try:
@@ -423,12 +424,12 @@ def _asym_worker(rank, world, port, out_dir):
 
 def test_sharded_lightgcn_rejects_asymmetric_normalisation(tmp_path):
     """D^-1 A + I is not symmetric: the row-sharded backward (pull over A[rows_g, :]) would be silently wrong."""
-    port = _free_port()
-    mp.spawn(_asym_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_asym_worker, args=(2, init, str(tmp_path)), nprocs=2, join=True)
     assert "not symmetric" in open(tmp_path / "msg.txt").read()
 
 
-def _ngcf_worker(rank, world, port, out_dir, n_chunks, restricted=False):
+def _ngcf_worker(rank, world, init, out_dir, n_chunks, restricted=False):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -436,7 +437,7 @@ def _ngcf_worker(rank, world, port, out_dir, n_chunks, restricted=False):
     from tagrec_amd import dist as TD
     from oracle import adj as oadj
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("ngcf_toy")
         csr = oadj.normalise(oadj.block_adjacency(*blocks_from_fixture(fx, 1)), "ngcf")
@@ -481,8 +482,8 @@ def test_row_sharded_ngcf_matches_reference_fixture(tmp_path, golden, world, n_c
     their gradients all-reduced) against the reference's own run: loss parts, every gradient, parameters after 3 steps.
     restricted: the compact restricted step (masked layer below the top, push-form top layer on the batch rows, flagged
     gradient exchange); the double leaves rows outside a mask as NaN, so a read of a row nobody computed fails."""
-    port = _free_port()
-    mp.spawn(_ngcf_worker, args=(world, port, str(tmp_path), n_chunks, restricted), nprocs=world, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_ngcf_worker, args=(world, init, str(tmp_path), n_chunks, restricted), nprocs=world, join=True)
     got = np.load(tmp_path / "ngcf.npz")
     fx = golden("ngcf_toy")
     np.testing.assert_allclose(got["losses"][0], fx["loss_parts"], rtol=1e-5)
@@ -531,7 +532,7 @@ def test_shard_helpers():
     assert a.tolist() == [0, 2, 2, 5] and c.tolist() == [0, 1, 2, 3, 4]
 
 
-def _fused_adam_worker(rank, world, port, out_dir, kind):
+def _fused_adam_worker(rank, world, init, out_dir, kind):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -539,7 +540,7 @@ def _fused_adam_worker(rank, world, port, out_dir, kind):
     from tagrec_amd import dist as TD
     from oracle import adj as oadj
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("lightgcn_toy")
         csr = oadj.normalise(oadj.block_adjacency(*blocks_from_fixture(fx, 1)), "bi_norm")
@@ -593,7 +594,7 @@ def _fused_adam_worker(rank, world, port, out_dir, kind):
 def test_sharded_step_with_adam_in_the_last_hop(tmp_path, kind, world):
     """`Adam.fuse_into(sharded model)`: the restricted step (reg == 0) applies the shard's update inside its last hop (per
     row block / on the column slice) -- same parameters after three steps as torch.optim.Adam on the gradient."""
-    port = _free_port()
-    mp.spawn(_fused_adam_worker, args=(world, port, str(tmp_path), kind), nprocs=world, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_fused_adam_worker, args=(world, init, str(tmp_path), kind), nprocs=world, join=True)
     got = np.load(tmp_path / "fused.npz")
     np.testing.assert_allclose(got["b"], got["a"], rtol=0, atol=2e-6)

@@ -4,7 +4,6 @@ kernel chain on column slices / row shards together with real inter-process redu
 group of ONE rank with every world-1 shortcut switched off (`dist.ALWAYS_COLLECTIVE`: the chunked asynchronous all-gathers,
 the flag gathers and the all-reduces all go through the "nccl" backend) and by `bench.py --gpus N` on a multi-GPU node."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -17,13 +16,15 @@ pytestmark = pytest.mark.gpu
 from conftest import ROOT, load_golden, blocks_from_fixture
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def _rendezvous(tmp_path):
+    """init_method of one group: a FileStore in a fresh directory of the test.  (A port picked free and released before
+    rank 0 listens on it lets a rank's retried connect() land on that very port -- a TCP self-connect -- or another
+    process take it.)"""
+    import tempfile
+    return "file://" + os.path.join(tempfile.mkdtemp(dir=tmp_path), "store")
 
 
-def _worker(rank, world, port, out_dir, kind, fixture="lightgcn_toy", backend="gloo"):
+def _worker(rank, world, init, out_dir, kind, fixture="lightgcn_toy", backend="gloo"):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -33,10 +34,10 @@ def _worker(rank, world, port, out_dir, kind, fixture="lightgcn_toy", backend="g
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     if backend == "nccl":                         # RCCL, one rank: run every collective anyway
-        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world, device_id=dev)
+        dist.init_process_group("nccl", init_method=init, rank=rank, world_size=world, device_id=dev)
         TD.ALWAYS_COLLECTIVE = True
     else:
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden(fixture)
         csr = oadj.normalise(oadj.block_adjacency(*blocks_from_fixture(fx, 1)), "bi_norm")
@@ -89,8 +90,8 @@ def _worker(rank, world, port, out_dir, kind, fixture="lightgcn_toy", backend="g
 def test_two_ranks_real_kernels(tmp_path, golden, kind, fixture):
     """Three Adam steps on two ranks against the parameters the REFERENCE reached (golden `step3`); the d256 fixture is
     C5's row width (3 layers), where the restricted row-sharded step uses all of: full layer, masked layer, push-form top."""
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, str(tmp_path), kind, fixture), nprocs=2, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_worker, args=(2, init, str(tmp_path), kind, fixture), nprocs=2, join=True)
     got = np.load(tmp_path / f"{kind}.npz")
     fx = golden(fixture)
     np.testing.assert_allclose(got["losses"][0], fx["loss_parts"], rtol=1e-5)
@@ -106,8 +107,8 @@ def test_rccl_group_of_one_runs_every_collective(tmp_path, golden, kind, fixture
     chunked async all_gather_into_tensor of float and uint8 blocks, all_reduce of the batch-row buffers, on the
     process group's streams -- API, dtype, contiguity and stream-ordering coverage a one-GPU box can give."""
     assert dist.is_nccl_available()
-    port = _free_port()
-    mp.spawn(_worker, args=(1, port, str(tmp_path), kind, fixture, "nccl"), nprocs=1, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_worker, args=(1, init, str(tmp_path), kind, fixture, "nccl"), nprocs=1, join=True)
     got = np.load(tmp_path / f"{kind}.npz")
     fx = golden(fixture)
     np.testing.assert_allclose(got["losses"][0], fx["loss_parts"], rtol=1e-5)
@@ -122,14 +123,14 @@ def _all_gather_list(t, world):
     return parts
 
 
-def _mid_worker(rank, world, port, out_dir, D, n_chunks, n_layer, kind="row"):
+def _mid_worker(rank, world, init, out_dir, D, n_chunks, n_layer, kind="row"):
     import sys
     sys.path.insert(0, ROOT)
     import tagrec_amd as T
     from tagrec_amd import dist as TD
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         nu, ni, B = 30_000, 20_000, 128
         ds = T.synth.make_bipartite_device(nu, ni, 1_500_000, seed=3, device=dev)      # same seed -> same graph on both ranks
@@ -188,8 +189,8 @@ def test_sharded_restricted_step_equals_single_gpu_model(tmp_path, D, n_chunks, 
     single-GPU restricted chain per column slice with the row norms / dots of the batch rows all-reduced -- against the
     one-GPU model computed on ALL rows: losses, table gradients, tables after two Adam steps (and, rows, the propagated
     tables).  D = 256 is the C5 row width."""
-    port = _free_port()
-    mp.spawn(_mid_worker, args=(2, port, str(tmp_path), D, n_chunks, n_layer, kind), nprocs=2, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_mid_worker, args=(2, init, str(tmp_path), D, n_chunks, n_layer, kind), nprocs=2, join=True)
     r = np.load(tmp_path / "mid.npz")
     for step in range(2):
         np.testing.assert_allclose(r[f"l2_{step}"], r[f"l1_{step}"], rtol=5e-6)
@@ -208,13 +209,14 @@ def test_sharded_restricted_step_equals_single_gpu_model(tmp_path, D, n_chunks, 
 def test_bench_starts_its_own_ranks(parallel):
     """`python bench.py --gpus 2` outside torch.distributed.run starts two fresh rank processes.  On a one-GPU box the
     ranks share cuda:0 and exchange through gloo (--share-gpu); what is checked is the launcher, the row-sharded step
-    end to end on a scaled-down C2 graph, and the shape of the JSON line."""
+    end to end on a scaled-down C2 graph, and the shape of the JSON line (--full: the collective probe and the per-step
+    waits are figures of the full run)."""
     import json
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--parallel", parallel, "--scale", "0.05", "--steps", "3",
-           "--warmup", "1", "--no-cpu", "--big-batch", "0"]
+           "--warmup", "1", "--full", "--no-cpu", "--big-batch", "0"]
     if torch.cuda.device_count() < 2:
         cmd.append("--share-gpu")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
@@ -231,7 +233,7 @@ def test_bench_starts_its_own_ranks(parallel):
     assert line["config"]["parallelism"].startswith(f"{parallel}-shard")
 
 
-def _ngcf_worker(rank, world, port, out_dir, restricted=False, backend="gloo"):
+def _ngcf_worker(rank, world, init, out_dir, restricted=False, backend="gloo"):
     import sys
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -241,10 +243,10 @@ def _ngcf_worker(rank, world, port, out_dir, restricted=False, backend="gloo"):
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     if backend == "nccl":
-        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world, device_id=dev)
+        dist.init_process_group("nccl", init_method=init, rank=rank, world_size=world, device_id=dev)
         TD.ALWAYS_COLLECTIVE = True
     else:
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     try:
         fx = load_golden("ngcf_toy")
         csr = oadj.normalise(oadj.block_adjacency(*blocks_from_fixture(fx, 1)), "ngcf")
@@ -280,8 +282,8 @@ def _ngcf_worker(rank, world, port, out_dir, restricted=False, backend="gloo"):
 
 def test_rccl_group_of_one_sharded_ngcf(tmp_path, golden):
     """The restricted row-sharded NGCF step over RCCL (group of one rank, shortcuts off)."""
-    port = _free_port()
-    mp.spawn(_ngcf_worker, args=(1, port, str(tmp_path), True, "nccl"), nprocs=1, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_ngcf_worker, args=(1, init, str(tmp_path), True, "nccl"), nprocs=1, join=True)
     got = np.load(tmp_path / "ngcf.npz")
     fx = golden("ngcf_toy")
     np.testing.assert_allclose(got["losses"][0], fx["loss_parts"], rtol=1e-5)
@@ -295,8 +297,8 @@ def test_two_ranks_row_sharded_ngcf_real_kernels(tmp_path, golden, restricted):
     """Row-sharded NGCF on two ranks with the real kernels (product on the rank's rows of A and of A^T, MFMA dense block,
     all-reduced W / b gradients) against the parameters the reference reached after three Adam steps; restricted = the
     compact restricted step (row-masked product / dense block / weight gradient, push-form top layer, flagged exchange)."""
-    port = _free_port()
-    mp.spawn(_ngcf_worker, args=(2, port, str(tmp_path), restricted), nprocs=2, join=True)
+    init = _rendezvous(tmp_path)
+    mp.spawn(_ngcf_worker, args=(2, init, str(tmp_path), restricted), nprocs=2, join=True)
     got = np.load(tmp_path / "ngcf.npz")
     fx = golden("ngcf_toy")
     np.testing.assert_allclose(got["losses"][0], fx["loss_parts"], rtol=1e-5)

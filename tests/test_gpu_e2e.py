@@ -383,3 +383,29 @@ def test_full_size_c4_training_step_restricted_equals_all_rows():
     assert not bad, (top, bad)
     del m, ds, res, g0, g1
     torch.cuda.empty_cache()
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` run on a scaled-down C2 graph: exactly --steps timed steps, the headline fields, none of the
+    --full figures, and --dump-outputs = the loss of the last timed step and the trained table (a fixed row sample)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.05", "--steps", "4",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(4 * 512 / (4 * line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["unit"] == "triplets/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["roofline"] is None and "configs" not in line["extra"] and "hip_graph_replay" not in line["extra"]
+    assert isinstance(line["cpu_baseline"], str) and line["cpu_baseline"].startswith("not run")
+    loss = np.load(out / "loss.npy")
+    assert loss.dtype == np.float64 and np.array_equal(loss, np.array(line["extra"]["last_loss"]))
+    table = np.load(out / "table.npy")
+    assert table.dtype == np.float32 and table.shape[1] == 64 and np.isfinite(table).all()
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20

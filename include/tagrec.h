@@ -284,6 +284,39 @@ int tagrec_slice_norm_bwd_f32(const float* X_raw, const float* inv, const float*
 int tagrec_row_softmax_fwd_f32(const tagrec_graph* g, const float* logits, float* a, void* stream);
 int tagrec_row_softmax_bwd_f32(const tagrec_graph* g, const float* a, const float* da, float* dlogits, void* stream);
 
+/* ---- DisenHAN relation attention (model/disenhan.py:28-97) ---------------------------------------------------------
+ * A relation is a merged CSR (int64 rowptr[n_rows+1], int32 col[nnz], fp32 mult[nnz]: the number of times the (row, col)
+ * pair occurs in the reference's uncoalesced COO), with row type a and column type b.  Per-node per-factor data
+ * [n, K]; embeddings [n, D] with factor k in columns [k D/K, (k+1) D/K).  No float atomics: bit-reproducible.
+ *   dh_edge_softmax_fwd : alpha[j] = softmax over row i's entries of  mult_j * sum_k r[i,k] relu(sL[i,k] + sR[col_j,k])
+ *   dh_edge_softmax_bwd : given dalpha: g[j] = mult_j * alpha_j (dalpha_j - sum_row alpha dalpha) (scratch [nnz]),
+ *                         dr / dsL [n_rows, K] (row sums), dsR [n_cols, K] (column sums over the transposed structure
+ *                         rowptr_t / col_t = row ids / perm = index of the entry in the row-major order)
+ *   dh_rel_epi_fwd      : Yl = leaky_0.2(Y);  Z[i, slice k] = Yl[i, slice k] W  (W [dk, dk]);
+ *                         r[i, :] = softmax_k < tanh(Z[i, slice k]), q >  (q [dk])
+ *   dh_rel_epi_bwd      : given dZ / dr (either may be NULL = 0): ds_k = r_k (dr_k - sum r dr),
+ *                         dZt = dZ + ds_k q (1 - tanh(Z)^2), dY = (dZt_k W^T) * leaky'(Yl), dsT = ds_k tanh(Z)
+ *                         (dW = Yl^T dZt and dq = column sums of dsT, both viewed [n K, dk], are left to the caller)
+ *   dh_combine_fwd      : x = ego + r1 (.) Z1 + r2 (.) Z2 per slice;  y = x / max(||x slice||, 1e-12);  inv as slice_norm
+ *   dh_combine_bwd      : dx = slice-norm backward of dy;  dZ_e = r_e (.) dx;  dr_e[i,k] = < Z_e[i, slice k], dx[i, slice k] >
+ * K in {1,2,4,8}; the row passes need D in {16,32,64,128,256}. */
+int tagrec_dh_edge_softmax_fwd_f32(const int64_t* rowptr, const int32_t* col, const float* mult, int64_t n_rows,
+                                   const float* sL, const float* sR, const float* r, int K, float* alpha, void* stream);
+int tagrec_dh_edge_softmax_bwd_f32(const int64_t* rowptr, const int32_t* col, const float* mult, int64_t n_rows,
+                                   const int64_t* rowptr_t, const int32_t* col_t, const int32_t* perm, int64_t n_cols,
+                                   const float* sL, const float* sR, const float* r, int K, const float* alpha,
+                                   const float* dalpha, float* g, float* dr, float* dsL, float* dsR, void* stream);
+int tagrec_dh_rel_epi_fwd_f32(const float* Y, const float* W, const float* q, int64_t n, int D, int K, float* Yl, float* Z,
+                              float* r, void* stream);
+int tagrec_dh_rel_epi_bwd_f32(const float* Yl, const float* Z, const float* r, const float* dZ, const float* dr,
+                              const float* W, const float* q, int64_t n, int D, int K, float* dY, float* dZt, float* dsT,
+                              void* stream);
+int tagrec_dh_combine_fwd_f32(const float* ego, const float* Z1, const float* r1, const float* Z2, const float* r2,
+                              int64_t n, int D, int K, float* x, float* y, float* inv, void* stream);
+int tagrec_dh_combine_bwd_f32(const float* x, const float* inv, const float* dy, const float* Z1, const float* r1,
+                              const float* Z2, const float* r2, int64_t n, int D, int K, float* dx, float* dZ1, float* dZ2,
+                              float* dr1, float* dr2, void* stream);
+
 /* ---- evaluation: sigmoid(U_b I^T) -> mask train positives -> top-K, fused (lightgcn.py:84-89, basic_test.py:36-50) --
  * U / I: propagated user / item tables, row-major [*, D].  users: int64 [n_users] ids to score.  train_ptr int64
  * [n_user_total + 1] / train_items int32: each user's train items, sorted (the rows basic_test.py:47 overwrites with

@@ -9,6 +9,7 @@ Reference name                      here
   model.help.split_mm / mul_loss ...  tagrec_amd.help
   model.LightGCN / NGCF / TGCN        tagrec_amd.LightGCN / NGCF / TGCN
   model.DGCF / DisenGCN / KGAT        tagrec_amd.DGCF / DisenGCN / KGAT
+  model.DisenHAN                      tagrec_amd.DisenHAN (disenhan_config(**kw))
   train_data.BPR_training_data        tagrec_amd.BPR_training_data
   training.Basic_train / Basic_test   tagrec_amd.Basic_train / Basic_test
   training.basic_train.epoch_training tagrec_amd.epoch_training
@@ -26,6 +27,7 @@ from .tgcn import TGCN  # noqa: F401
 from .dgcf import DGCF  # noqa: F401
 from .disengcn import DisenGCN  # noqa: F401
 from .kgat import KGAT  # noqa: F401
+from .disenhan import DisenHAN, disenhan_config  # noqa: F401
 from .train import Adam, Basic_train, Early_stop, GraphedStep, epoch_training  # noqa: F401
 from .train_data import (Abstract_training_data, BPR_training_data, DGCF_training_data,  # noqa: F401
                          Fixed_training_data, KGAT_training_data, TransTag_training_data)

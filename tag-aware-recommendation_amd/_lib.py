@@ -136,6 +136,13 @@ _SIGNATURES = {
     "tagrec_spmm_listed_workspace": [c_int64, c_int],
     "tagrec_spmm_listed_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p],
     "tagrec_row_flags_f32": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
+    "tagrec_dh_edge_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "tagrec_dh_edge_softmax_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_dh_rel_epi_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_dh_rel_epi_bwd_f32": [c_void_p] * 7 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_dh_combine_fwd_f32": [c_void_p] * 5 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_dh_combine_bwd_f32": [c_void_p] * 7 + [c_int64, c_int, c_int] + [c_void_p] * 6,
     "tagrec_eval_topk_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                              c_void_p, c_void_p],
     "tagrec_sample_negative_i64": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p],

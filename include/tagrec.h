@@ -327,6 +327,17 @@ int tagrec_eval_topk_f32(const float* U, const float* I, int64_t n_item, int D, 
                          int64_t n_users, const int64_t* train_ptr, const int32_t* train_items, int K,
                          int64_t* top_idx, float* top_val, void* stream);
 
+/* ---- evaluation with AUC: the same pass, plus each user's AUC over its un-masked items (basic_test.py:53,73) --------
+ * test_ptr int64 [n_user_total + 1] / test_items int32: each user's test items, sorted (duplicates allowed).  valid =
+ * not a train id; positives = unique test ids that are valid; negatives = the other valid items.  Per evaluated user:
+ * n_pos / n_neg int64 [n_users], auc_num2 int64 [n_users] = sum over (positive p, negative x) of 2 [s_p > s_x] +
+ * [s_p == s_x], with s = the fp32 sigmoid score the top-K ranks by; AUC = auc_num2 / (2 n_pos n_neg).  top_idx /
+ * top_val exactly as tagrec_eval_topk_f32.  Same widths, K <= 64. */
+int tagrec_eval_topk_auc_f32(const float* U, const float* I, int64_t n_item, int D, const int64_t* users,
+                             int64_t n_users, const int64_t* train_ptr, const int32_t* train_items,
+                             const int64_t* test_ptr, const int32_t* test_items, int K, int64_t* top_idx,
+                             float* top_val, int64_t* auc_num2, int64_t* n_pos, int64_t* n_neg, void* stream);
+
 /* ---- negative sampler (train_data/utils.py:19-28, 31-40) -------------------------------------------------------
  * For each of n_rows positive rows with left id left[e] (a user, or a (user, tag) pair id): one uniform draw in
  * [0, n_right), re-drawn while it is in the left id's sorted positive list cols[rowptr[l] .. rowptr[l+1]).

@@ -12,6 +12,7 @@ Reference name                      here
   model.DisenHAN                      tagrec_amd.DisenHAN (disenhan_config(**kw))
   train_data.BPR_training_data        tagrec_amd.BPR_training_data
   training.Basic_train / Basic_test   tagrec_amd.Basic_train / Basic_test
+  training.utils.user_group_split     tagrec_amd.user_group_split
   training.basic_train.epoch_training tagrec_amd.epoch_training
   utility.word.CFG                    tagrec_amd.CFG (get_config(model, **kw))
 """
@@ -19,7 +20,7 @@ from . import synth  # noqa: F401
 from . import _lib, config, data, graph, help  # noqa: F401
 from ._lib import TagrecError  # noqa: F401
 from .config import CFG, get_config, init_seed  # noqa: F401
-from .evaluate import Basic_test  # noqa: F401
+from .evaluate import Basic_test, user_group_split  # noqa: F401
 from .graph import Graph, creat_adj  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
 from .ngcf import NGCF  # noqa: F401

@@ -226,7 +226,8 @@ int tagrec_rownorm_bwd_f32(const float* X_raw, const float* inv_norm, const floa
  * the rows the L2 term reads (ego tables for LightGCN, the propagated ones for NGCF/TGCN).
  * fwd writes loss_out[0] = mul_loss, loss_out[1] = l2reg_loss (unweighted), and coef[b] =
  * d mul_loss_b / d(neg_b - pos_b) (a sigmoid) for the backward.  `partials` is scratch of
- * 2*ceil(B/256) floats; the two-stage reduction is deterministic. */
+ * 2*ceil(B/4) floats (two per launched block, four triplets per block); the two-stage reduction is
+ * deterministic. */
 int tagrec_bpr_fwd_f32(const float* U, const float* I, int64_t ld, int D,
                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
                        const int64_t* trip, int64_t B, int loss_kind,

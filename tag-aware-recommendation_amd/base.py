@@ -7,6 +7,29 @@ import torch.nn as nn
 from . import _lib
 
 
+def layer_seed(seed, k):
+    """Seed of layer k's dropout mask within the forward pass seeded `seed`."""
+    return (int(seed) * 64 + k) & 0xFFFFFFFFFFFFFFFF
+
+
+def scatter_rows(n, rows, compact):
+    """[n, D] tensor that holds sum of compact[j] over rows[j] == r at the listed rows and is UNWRITTEN elsewhere."""
+    t = torch.empty(n, compact.shape[1], dtype=torch.float32, device=compact.device)
+    t.index_fill_(0, rows, 0.0)
+    return t.index_add_(0, rows, compact)
+
+
+def fused_last_hop(graph_t, fused, g, flags, count, addend, s, b_flags):
+    """The backward product that lands on the table, A^T g + s * addend, with Adam applied in its epilogue: fused =
+    (table, optimizer); no gradient tensor is written.  The step is committed after the launch, so a launch that fails
+    leaves no mark on the optimizer."""
+    table, opt = fused
+    m, v, step = opt.fused_state(table)
+    graph_t.spmm_axpy_adam(g, flags, count, addend, s, b_flags, table.data, m, v, opt.lr, opt.betas, opt.eps, step,
+                           opt.fused_dev(table))
+    opt.fused_commit(table)
+
+
 def xavier_tables(num_list, dim, device):
     """xavier_uniform_ per table, in order, drawn from torch's CPU generator so a seeded run
     reproduces the reference's initial values (lightgcn.py:37-47)."""
@@ -112,6 +135,36 @@ class TableModel(nn.Module):
             all_users, all_items = self._eval_cache
         users = users.to(self.table.device)
         return torch.sigmoid(torch.matmul(all_users[users], all_items.t()))
+
+
+class FusedStepModel(TableModel):
+    """What LightGCN and NGCF share beyond the table: the hook `Adam.fuse_into(model)` looks for, and the per-step seed of
+    the library's counter-based message dropout."""
+
+    fused_capturable = True        # Adam(capturable=True).fuse_into(model): the fused update advances its counter on the device
+    _drop_rates = list             # the container the rates are handed over in
+
+    def set_fused_optimizer(self, opt):
+        """`Adam.fuse_into(model)`: the compact restricted step applies the table's Adam update in the epilogue of the
+        product that lands on it; every other path hands the optimizer a gradient as usual.  None switches it off."""
+        self._fused_opt = opt
+
+    def _check_drop_width(self):
+        """Raise if the fused dropout kernels cannot serve this model's width."""
+
+    def _drops(self):
+        """(per-layer drop rates, seed of this forward pass) when message dropout is active, else (None, 0).  The
+        seed advances with every training-mode forward pass; masks are functions of (seed, layer, element)."""
+        drops = [float(p) for p in self.message_drop_list[:self.num_layer]]
+        if not (self.training and any(p > 0 for p in drops)):
+            return None, 0
+        self._check_drop_width()
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.TagrecError(f"{type(self).__name__}: message dropout draws a new seed on the host every step and "
+                                   "cannot be captured in a HIP graph")
+        self._drop_calls = getattr(self, "_drop_calls", 0) + 1
+        return (self._drop_rates(drops + [0.0] * (self.num_layer - len(drops))),
+                (int(self.drop_seed) << 24) + self._drop_calls)
 
 
 def _split_table_hook(module, state_dict, prefix, local_metadata):

@@ -31,9 +31,10 @@ tests/ with a test double; the product default `HipOps` is the HIP library and n
 import torch
 import torch.distributed as dist
 
-from . import _lib, help as H
+from . import _lib, help as H, rowops
 from .graph import Graph
 from .lightgcn import xavier_tables
+from .rowops import VEC_WIDTHS, batch_rows, compact_triplets
 from .train import fused_optimizer
 
 
@@ -57,8 +58,7 @@ class HipOps:
                                                          _lib.stream_ptr()), "graph_mark_cols")
 
     def spmm_listed(self, g, rows, x, out):
-        from .lightgcn import spmm_listed
-        spmm_listed(g, rows, x, out)
+        g.spmm_listed(rows, x, out)
 
     def layer_fwd(self, g, x_full, y, inv, acc, s, row_mask=None):
         """acc None: the layer mean is not accumulated.  row_mask: only these rows are computed / written."""
@@ -89,44 +89,19 @@ class HipOps:
         g.spmm_axpy_adam(g_in, in_flags, in_count, b, s, b_flags, p, m, v, lr, betas, eps, step)
 
     def rownorm_fwd(self, x):
-        n, D = x.shape
-        z = torch.empty_like(x)
-        inv = torch.empty(n, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().tagrec_rownorm_fwd_f32(_lib.ptr(x), _lib.ptr(z), D, _lib.ptr(inv), n, D, _lib.stream_ptr()),
-                   "rownorm_fwd")
-        return z, inv
+        return rowops.rownorm_fwd(x)
 
     def rownorm_bwd(self, x_raw, inv, dz, s, out):
-        n, D = x_raw.shape
-        _lib.check(_lib.load().tagrec_rownorm_bwd_f32(_lib.ptr(x_raw), _lib.ptr(inv), _lib.ptr(dz), D, s,
-                                                      _lib.ptr(out), 0, n, D, _lib.stream_ptr()), "rownorm_bwd")
+        rowops.rownorm_bwd(x_raw, inv, dz, s, out)
 
     def rownorm_bwd_flags(self, x_raw, inv, dz, s, out):
-        n, D = x_raw.shape
-        flags = torch.empty(n, dtype=torch.uint8, device=out.device)
-        cnt = torch.zeros(1, dtype=torch.int32, device=out.device)
-        _lib.check(_lib.load().tagrec_rownorm_bwd_flags_f32(_lib.ptr(x_raw), _lib.ptr(inv), _lib.ptr(dz), D, s, _lib.ptr(out), 0,
-                                                            n, D, _lib.ptr(flags), _lib.ptr(cnt), _lib.stream_ptr()),
-                   "rownorm_bwd_flags")
-        return flags
+        return rowops.rownorm_bwd_flags(x_raw, inv, dz, s, out)[0]
 
     def bpr_fwd(self, U, I, Ur, Ir, trip, kind):
-        B, D = trip.shape[0], U.shape[1]
-        coef = torch.empty(B, dtype=torch.float32, device=U.device)
-        partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=U.device)
-        res = torch.empty(2, dtype=torch.float32, device=U.device)
-        _lib.check(_lib.load().tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), D, D, _lib.ptr(Ur), _lib.ptr(Ir), D, D,
-                                                  _lib.ptr(trip), B, kind, _lib.ptr(coef), _lib.ptr(partials),
-                                                  _lib.ptr(res), _lib.stream_ptr()), "bpr_fwd")
-        return res, coef
+        return rowops.bpr_fwd(U, I, Ur, Ir, trip, kind)
 
     def bpr_bwd(self, U, I, Ur, Ir, trip, coef, g, dU, dI, dUr, dIr):
-        B, D = trip.shape[0], U.shape[1]
-        _lib.check(_lib.load().tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), D, D, _lib.ptr(Ur), _lib.ptr(Ir), D, D,
-                                                  _lib.ptr(trip), B, _lib.ptr(coef), _lib.ptr(g), 1.0, _lib.ptr(dU),
-                                                  _lib.ptr(dI), _lib.ptr(dUr), _lib.ptr(dIr), _lib.stream_ptr()),
-                   "bpr_bwd")
-
+        rowops.bpr_bwd(U, I, Ur, Ir, trip, coef, g, dU, dI, dUr, dIr)
 
     # -- NGCF dense block (csrc/ngcf.hip)
     def ngcf_dense_fwd(self, nei, x, w1p, w2p, xp, inv, z_slot, ldz, row_mask=None):
@@ -189,11 +164,7 @@ class HipOps:
     sparse_backward = True
 
     def row_flags(self, x):
-        flags = torch.empty(x.shape[0], dtype=torch.uint8, device=x.device)
-        count = torch.zeros(1, dtype=torch.int32, device=x.device)
-        _lib.check(_lib.load().tagrec_row_flags_f32(_lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(flags), _lib.ptr(count),
-                                                    _lib.stream_ptr()), "row_flags")
-        return flags, count
+        return rowops.row_flags(x)
 
     def spmm_normbwd_dot_sparse(self, g, g_in, fl, x_raw, inv, dz, dot, s, out, row_mask=None):
         """row_mask: only these rows can be non-zero (see lightgcn.propagate_backward); the others are zero-filled here
@@ -213,11 +184,7 @@ class HipOps:
         g.spmm_axpy_sparse(g_in, fl[0], fl[1], b, s, out)
 
     def bpr_dots(self, U, I, Ur, Ir, trip):
-        B, D = trip.shape[0], U.shape[1]
-        dots = torch.empty(B, 3, dtype=torch.float32, device=U.device)
-        _lib.check(_lib.load().tagrec_bpr_dots_f32(_lib.ptr(U), _lib.ptr(I), D, D, _lib.ptr(Ur), _lib.ptr(Ir), D, D,
-                                                   _lib.ptr(trip), B, _lib.ptr(dots), _lib.stream_ptr()), "bpr_dots")
-        return dots
+        return rowops.bpr_dots(U, I, Ur, Ir, trip)
 
 
 # Tests set this to run every collective through torch.distributed even in a group of ONE rank (where the models would
@@ -367,11 +334,11 @@ class _ShardedLoss(torch.autograd.Function):
         B = trip.shape[0]
         T = 3 * B
         dev = x0.device
-        rows = torch.cat([trip[:, 0], m.n_user + trip[:, 1], m.n_user + trip[:, 2]])      # original node ids, [T]
+        rows = batch_rows(trip, m.n_user)      # original node ids, [T]
         rows_p = part.gathered(rows)
         slot = torch.nonzero(part.owner(rows) == m.rank).flatten()                       # batch slots this rank owns
         loc = rows[slot] - m.lo
-        vec = D in (8, 16, 32, 64, 128, 256)
+        vec = D in VEC_WIDTHS
         restricted = bool(m.restrict_forward and getattr(ops, "restrict_forward", False) and L >= 1 and vec
                           and T * m.restrict_min_ratio <= part.n)
         raws, invs = [], []
@@ -426,8 +393,7 @@ class _ShardedLoss(torch.autograd.Function):
             y_top = buf[2]
             z_top, inv_top = ops.rownorm_fwd(y_top)
             out_b = out_b + s * z_top
-        ar = torch.arange(B, device=dev)
-        ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
+        ctrip = compact_triplets(B, dev)
         res, coef = ops.bpr_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip, H.loss_kind_id(m.loss_func))
         ctx.m, ctx.raws, ctx.invs, ctx.restricted, ctx.mid_mask = m, raws, invs, restricted, mid_mask
         ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.coef = out_b.contiguous(), ego_b, ctrip, coef
@@ -445,7 +411,7 @@ class _ShardedLoss(torch.autograd.Function):
         L, s = m.num_layer, 1.0 / (m.num_layer + 1)
         dev = out_b.device
         restricted = ctx.restricted
-        vec = D in (8, 16, 32, 64, 128, 256)
+        vec = D in VEC_WIDTHS
         sparse = vec and getattr(ops, "row_sparse_backward", False)
         d_b = torch.zeros(2, T, D, dtype=torch.float32, device=dev)        # d loss / d out_b, d loss / d ego_b (replicated)
         ops.bpr_bwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip, ctx.coef, g.contiguous(),
@@ -736,7 +702,7 @@ class _ShardedNgcfRestrictedLoss(torch.autograd.Function):
         wps = _wps([t.detach() for t in mats])
         B = trip.shape[0]
         T = 3 * B
-        rows = torch.cat([trip[:, 0], m.n_user + trip[:, 1], m.n_user + trip[:, 2]])      # original node ids, [T]
+        rows = batch_rows(trip, m.n_user)      # original node ids, [T]
         rows_p = part.gathered(rows)
         slot = torch.nonzero(part.owner(rows) == m.rank).flatten()                       # batch slots this rank owns
         loc = rows[slot] - m.lo
@@ -781,8 +747,7 @@ class _ShardedNgcfRestrictedLoss(torch.autograd.Function):
         out_b = torch.empty(T, dtot, dtype=torch.float32, device=dev)
         out_b[:, :dlow] = buf[:, :dlow]
         ops.ngcf_dense_fwd(nc, xc, w1p, w2p, xpc, invc, out_b[:, dlow:], dtot)
-        ar = torch.arange(B, device=dev)
-        ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
+        ctrip = compact_triplets(B, dev)
         res, coef = ops.bpr_fwd(out_b[:B], out_b[B:], out_b[:B], out_b[B:], ctrip, H.loss_kind_id(m.loss_func))
         ctx.m, ctx.saved, ctx.mid, ctx.top = m, saved, mid, (nc, xc, xpc, invc, w1p, w2p)
         ctx.out_b, ctx.ctrip, ctx.coef, ctx.rows_p, ctx.slot, ctx.loc = out_b, ctrip, coef, rows_p, slot, loc
@@ -892,14 +857,13 @@ class _ShardedNgcfLoss(torch.autograd.Function):
             x, off = xp, off + dims[k + 1]
         B = trip.shape[0]
         T = 3 * B
-        rows = torch.cat([trip[:, 0], m.n_user + trip[:, 1], m.n_user + trip[:, 2]])
+        rows = batch_rows(trip, m.n_user)
         slot = torch.nonzero(part.owner(rows) == m.rank).flatten()
         loc = rows[slot] - m.lo
         out_b = torch.zeros(T, dtot, dtype=torch.float32, device=dev)
         out_b.index_copy_(0, slot, out.index_select(0, loc))
         m.all_reduce(out_b, "batch_rows")
-        ar = torch.arange(B, device=dev)
-        ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
+        ctrip = compact_triplets(B, dev)
         res, coef = ops.bpr_fwd(out_b[:B], out_b[B:], out_b[:B], out_b[B:], ctrip, H.loss_kind_id(m.loss_func))
         ctx.m, ctx.saved, ctx.out_b, ctx.ctrip, ctx.coef, ctx.slot, ctx.loc = m, saved, out_b, ctrip, coef, slot, loc
         return res
@@ -1028,7 +992,7 @@ class ShardedNGCF(torch.nn.Module):
 
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
-        vec = all(d in (8, 16, 32, 64, 128, 256) for d in self.dims)
+        vec = all(d in VEC_WIDTHS for d in self.dims)
         restricted = (self.restrict_forward and getattr(self.ops, "restrict_forward", False) and vec
                       and 3 * batch_data.shape[0] * self.restrict_min_ratio <= self.part.n)
         fn = _ShardedNgcfRestrictedLoss if restricted else _ShardedNgcfLoss
@@ -1053,7 +1017,7 @@ class _FeatureRestrictedLoss(torch.autograd.Function):
         n, Dl = x0.shape
         B = trip.shape[0]
         dev = x0.device
-        rows = torch.cat([trip[:, 0], m.n_user + trip[:, 1], m.n_user + trip[:, 2]])
+        rows = batch_rows(trip, m.n_user)
         mid = ops.mark_rows(m.graph, rows, torch.zeros(n, dtype=torch.uint8, device=dev)) if L >= 2 else None
         raws = []
         x = x0
@@ -1072,8 +1036,7 @@ class _FeatureRestrictedLoss(torch.autograd.Function):
         out_b = ego_b * s
         for a, iv in zip(at_rows, inv):
             out_b.addcmul_(a, iv[:, None], value=s)
-        ar = torch.arange(B, device=dev)
-        ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
+        ctrip = compact_triplets(B, dev)
         dots = ops.bpr_dots(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip)
         m.all_reduce(dots)                                                   # full-width scores and L2 term
         xd = dots[:, 1] - dots[:, 0]                                         # neg - pos
@@ -1155,8 +1118,8 @@ class _FeatureShardedLoss(torch.autograd.Function):
         masks = {}
         nu = m.n_user
         if (getattr(m.ops, "restrict_forward", False) and L >= 1 and trip.shape[0] * 48 <= n
-                and x0.shape[1] in (8, 16, 32, 64, 128, 256)):
-            rows = torch.cat([trip[:, 0], trip[:, 1] + nu, trip[:, 2] + nu])
+                and x0.shape[1] in VEC_WIDTHS):
+            rows = batch_rows(trip, nu)
             top = torch.zeros(n, dtype=torch.uint8, device=x0.device)
             top.index_fill_(0, rows, 1)
             masks[L - 1] = top
@@ -1212,7 +1175,7 @@ class _FeatureShardedLoss(torch.autograd.Function):
             gl = torch.empty_like(d_out)
             m.ops.rownorm_bwd_dot(raws[L - 1], invs[L - 1], d_out, dots[L - 1], s, gl)
             # the gradient spreads from the batch rows by one hop per product: rows still zero are not gathered
-            sparse = getattr(m.ops, "sparse_backward", False) and x0.shape[1] in (8, 16, 32, 64, 128, 256)
+            sparse = getattr(m.ops, "sparse_backward", False) and x0.shape[1] in VEC_WIDTHS
             fl = m.ops.row_flags(gl) if sparse else None
             for k in range(L - 2, -1, -1):
                 gn = torch.empty_like(d_out)
@@ -1292,7 +1255,7 @@ class FeatureShardedLightGCN(torch.nn.Module):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         restricted = (self.restrict_forward and getattr(self.ops, "restrict_forward", False) and self.num_layer >= 1
-                      and self.dim_local in (8, 16, 32, 64, 128, 256)
+                      and self.dim_local in VEC_WIDTHS
                       and 3 * batch_data.shape[0] * self.restrict_min_ratio <= self.n_nodes)
         fn = _FeatureRestrictedLoss if restricted else _FeatureShardedLoss
         res = fn.apply(self.table, self, batch_data)

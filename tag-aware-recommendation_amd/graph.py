@@ -358,6 +358,18 @@ class Graph:
                    _lib.stream_ptr())
         return out
 
+    def spmm_listed(self, rows, X, out=None):
+        """(A X)[rows] as a compact [len(rows), D] tensor (rows int64, may repeat)."""
+        rows = rows.contiguous()
+        lib = _lib.load()
+        if out is None:
+            out = torch.empty(rows.numel(), X.shape[1], dtype=torch.float32, device=X.device)
+        ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), X.shape[1])
+        ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
+        self._call("spmm_listed", lib.tagrec_spmm_listed_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
+                   _lib.ptr(out), X.shape[1], _lib.ptr(ws), ws_n, _lib.stream_ptr())
+        return out
+
     def spmm_norm_acc_rows(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, drop_p=0.0, seed=0):
         """`spmm_norm_acc` for the rows with row_mask[r] != 0 only (the others are left as they are; None = every row).
         acc None: the layer mean is not accumulated."""

@@ -12,7 +12,7 @@ Inputs must be GPU tensors; there is no CPU path.
 """
 import torch
 
-from . import _lib
+from . import _lib, rowops
 from .graph import Graph, coalesce_device, creat_adj  # noqa: F401  (creat_adj re-exported)
 
 
@@ -48,23 +48,14 @@ class _RowNormalize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X):
         X = _lib.require_gpu_tensor(X.contiguous(), torch.float32, "normalize_rows input")
-        n, D = X.shape
-        Z = torch.empty_like(X)
-        inv = torch.empty(n, dtype=torch.float32, device=X.device)
-        _lib.check(_lib.load().tagrec_rownorm_fwd_f32(_lib.ptr(X), _lib.ptr(Z), D, _lib.ptr(inv), n, D,
-                                                      _lib.stream_ptr()), "rownorm_fwd")
+        Z, inv = rowops.rownorm_fwd(X)
         ctx.save_for_backward(X, inv)
         return Z
 
     @staticmethod
     def backward(ctx, dZ):
         X, inv = ctx.saved_tensors
-        dZ = dZ.contiguous()
-        n, D = X.shape
-        dX = torch.empty_like(X)
-        _lib.check(_lib.load().tagrec_rownorm_bwd_f32(_lib.ptr(X), _lib.ptr(inv), _lib.ptr(dZ), D, 1.0, _lib.ptr(dX),
-                                                      0, n, D, _lib.stream_ptr()), "rownorm_bwd")
-        return dX
+        return rowops.rownorm_bwd(X, inv, dZ.contiguous(), 1.0, torch.empty_like(X))
 
 
 def normalize_rows(x):
@@ -77,20 +68,11 @@ class _TripletLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, I, Ureg, Ireg, trip, loss_kind):
-        lib = _lib.load()
         for t, nm in ((U, "U"), (I, "I")):
             _lib.require_gpu_tensor(t, torch.float32, "bpr " + nm)
         trip = _lib.require_gpu_tensor(trip.contiguous(), torch.int64, "bpr triplets")
-        B, D = trip.shape[0], U.shape[1]
         has_reg = Ureg is not None
-        coef = torch.empty(B, dtype=torch.float32, device=U.device)
-        partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=U.device)
-        out = torch.empty(2, dtype=torch.float32, device=U.device)
-        _lib.check(lib.tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), U.stride(0), D,
-                                          _lib.ptr(Ureg), _lib.ptr(Ireg), Ureg.stride(0) if has_reg else 0,
-                                          Ureg.shape[1] if has_reg else 0, _lib.ptr(trip), B, loss_kind,
-                                          _lib.ptr(coef), _lib.ptr(partials), _lib.ptr(out), _lib.stream_ptr()),
-                   "bpr_fwd")
+        out, coef = rowops.bpr_fwd(U, I, Ureg, Ireg, trip, loss_kind)
         ctx.save_for_backward(U, I, Ureg if has_reg else U.new_empty(0), Ireg if has_reg else U.new_empty(0), trip, coef)
         ctx.has_reg = has_reg
         ctx.same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr()
@@ -99,20 +81,14 @@ class _TripletLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         U, I, Ureg, Ireg, trip, coef = ctx.saved_tensors
-        g = g.contiguous()
         dU, dI = torch.zeros_like(U), torch.zeros_like(I)
         if ctx.has_reg and not ctx.same:
             dUr, dIr = torch.zeros_like(Ureg), torch.zeros_like(Ireg)
         elif ctx.has_reg:
             dUr, dIr = dU, dI
         else:
-            dUr = dIr = None
-        _lib.check(_lib.load().tagrec_bpr_bwd_f32(
-            _lib.ptr(U), _lib.ptr(I), U.stride(0), U.shape[1],
-            _lib.ptr(Ureg if ctx.has_reg else None), _lib.ptr(Ireg if ctx.has_reg else None),
-            Ureg.stride(0) if ctx.has_reg else 0, Ureg.shape[1] if ctx.has_reg else 0,
-            _lib.ptr(trip), trip.shape[0], _lib.ptr(coef), _lib.ptr(g), 1.0,
-            _lib.ptr(dU), _lib.ptr(dI), _lib.ptr(dUr), _lib.ptr(dIr), _lib.stream_ptr()), "bpr_bwd")
+            dUr = dIr = Ureg = Ireg = None
+        rowops.bpr_bwd(U, I, Ureg, Ireg, trip, coef, g, dU, dI, dUr, dIr)
         if ctx.has_reg and ctx.same:
             return dU, dI, None, None, None, None
         return dU, dI, (dUr if ctx.has_reg else None), (dIr if ctx.has_reg else None), None, None
@@ -132,9 +108,7 @@ def triplet_loss(U, I, Ureg, Ireg, trip, loss_func):
 
 def mul_loss(users_emb, pos_emb, neg_emb, loss_func):
     """`mul_loss` on already gathered rows (loss.py:4-12)."""
-    B = users_emb.shape[0]
-    ar = torch.arange(B, device=users_emb.device)
-    trip = torch.stack([ar, ar, ar + B], dim=1)
+    trip = rowops.compact_triplets(users_emb.shape[0], users_emb.device)
     items = torch.cat([pos_emb, neg_emb], dim=0)
     return _TripletLoss.apply(users_emb.contiguous(), items, None, None, trip, loss_kind_id(loss_func))[0]
 
@@ -173,10 +147,11 @@ class _TransTagLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         Eu, Ei, Et, quad, dist = ctx.saved_tensors
+        g = g.contiguous()
         dEu, dEi, dEt = torch.zeros_like(Eu), torch.zeros_like(Ei), torch.zeros_like(Et)
         _lib.check(_lib.load().tagrec_transtag_bwd_f32(_lib.ptr(Eu), _lib.ptr(Ei), _lib.ptr(Et), Eu.stride(0), Eu.shape[1],
                                                        _lib.ptr(quad), quad.shape[0], ctx.margin, _lib.ptr(dist),
-                                                       _lib.ptr(g.contiguous()), _lib.ptr(dEu), _lib.ptr(dEi), _lib.ptr(dEt),
+                                                       _lib.ptr(g), _lib.ptr(dEu), _lib.ptr(dEi), _lib.ptr(dEt),
                                                        _lib.stream_ptr()), "transtag_bwd")
         return dEu, dEi, dEt, None, None
 

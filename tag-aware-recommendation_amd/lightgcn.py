@@ -14,15 +14,13 @@ Differences in mechanism, not in results:
 """
 import torch
 
-from . import _lib, help as H
-from .base import StepWorkspace, TableModel, _Token, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
+from . import _lib, help as H, rowops
+from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
+from .base import layer_seed as _layer_seed
 from .config import CFG as _GLOBAL_CFG
 from .graph import Graph, creat_adj
+from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
-
-
-def _layer_seed(seed, k):
-    return (int(seed) * 64 + k) & 0xFFFFFFFFFFFFFFFF
 
 
 def propagate_forward(graph, x0, n_layer, drops=None, seed=0, loss_rows=None, masks_out=None):
@@ -40,7 +38,7 @@ def propagate_forward(graph, x0, n_layer, drops=None, seed=0, loss_rows=None, ma
     raws, invs = [], []
     x = x0
     masks = {}
-    if (loss_rows is not None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and x0.shape[1] in (8, 16, 32, 64, 128, 256)
+    if (loss_rows is not None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and x0.shape[1] in VEC_WIDTHS
             and loss_rows.numel() * 16 <= x0.shape[0]):              # a batch that touches most rows gains nothing
         top = torch.zeros(x0.shape[0], dtype=torch.uint8, device=x0.device)
         top.index_fill_(0, loss_rows, 1)
@@ -80,21 +78,17 @@ def propagate_backward(graph_t, d_out, raws, invs, drops=None, seed=0, masks=Non
     if L == 0:
         return d_out.clone()
     n, D = d_out.shape
-    lib = _lib.load()
     g = torch.empty_like(d_out)
     # The gradient is non-zero on the batch rows only at the head of the chain and spreads by one hop per layer:
     # every product is told which rows of its operand hold a non-zero and leaves the others unfetched (bit-identical
     # result; the kernel ignores the flags once they cover 4/5 of the rows, without a host round trip).
-    sparse = D in (8, 16, 32, 64, 128, 256)
+    sparse = D in VEC_WIDTHS
     if sparse:
         flags = [torch.empty(n, dtype=torch.uint8, device=d_out.device) for _ in range(2)]
         counts = torch.zeros(2, dtype=torch.int32, device=d_out.device)
-        _lib.check(lib.tagrec_rownorm_bwd_flags_f32(_lib.ptr(raws[L - 1]), _lib.ptr(invs[L - 1]), _lib.ptr(d_out), D, s,
-                                                    _lib.ptr(g), 0, n, D, _lib.ptr(flags[0]), _lib.ptr(counts[0:1]),
-                                                    _lib.stream_ptr()), "rownorm_bwd_flags")
+        rowops.rownorm_bwd_flags(raws[L - 1], invs[L - 1], d_out, s, g, flags[0], counts[0:1])
     else:
-        _lib.check(lib.tagrec_rownorm_bwd_f32(_lib.ptr(raws[L - 1]), _lib.ptr(invs[L - 1]), _lib.ptr(d_out), D, s,
-                                              _lib.ptr(g), 0, n, D, _lib.stream_ptr()), "rownorm_bwd")
+        rowops.rownorm_bwd(raws[L - 1], invs[L - 1], d_out, s, g)
     if drops and drops[L - 1] > 0:
         H.message_drop(g, drops[L - 1], _layer_seed(seed, L - 1), out=g)     # flags stay a superset of the non-zero rows
     cur = 0
@@ -111,11 +105,7 @@ def propagate_backward(graph_t, d_out, raws, invs, drops=None, seed=0, masks=Non
             graph_t.spmm_normbwd(g, raws[k], invs[k], d_out, s, gn, drops[k] if drops else 0.0, _layer_seed(seed, k))
         g = gn
     if fused is not None and sparse:      # (table, optimizer): Adam in the epilogue of the last hop, no gradient tensor
-        table, opt = fused
-        m, v, step = opt.fused_state(table)
-        graph_t.spmm_axpy_adam(g, flags[cur], counts[cur:cur + 1], d_out, s, None, table.data, m, v, opt.lr, opt.betas, opt.eps, step,
-                               opt.fused_dev(table))
-        opt.fused_commit(table)
+        fused_last_hop(graph_t, fused, g, flags[cur], counts[cur:cur + 1], d_out, s, None)
         return None
     g0 = torch.empty_like(d_out)
     if sparse:
@@ -125,20 +115,9 @@ def propagate_backward(graph_t, d_out, raws, invs, drops=None, seed=0, masks=Non
     return g0
 
 
-VEC_WIDTHS = (8, 16, 32, 64, 128, 256)
-
-
 def spmm_listed(graph, rows, x, out=None):
     """(A x)[rows] as a compact [len(rows), D] tensor (rows int64, may repeat)."""
-    rows = rows.contiguous()
-    lib = _lib.load()
-    if out is None:
-        out = torch.empty(rows.numel(), x.shape[1], dtype=torch.float32, device=x.device)
-    ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), x.shape[1])
-    ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=x.device)
-    graph._call("spmm_listed", lib.tagrec_spmm_listed_f32, graph.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(x),
-                _lib.ptr(out), x.shape[1], _lib.ptr(ws), ws_n, _lib.stream_ptr())
-    return out
+    return graph.spmm_listed(rows, x, out)
 
 
 def restricted_forward(graph, x0, n_layer, rows, ws=None):
@@ -150,7 +129,6 @@ def restricted_forward(graph, x0, n_layer, rows, ws=None):
     UNWRITTEN in its output; every later reader is told which rows are valid."""
     L, s = n_layer, 1.0 / (n_layer + 1)
     n, D = x0.shape
-    T = rows.numel()
     dev = x0.device
     mid = graph.mark_rows(rows, step_buffer(ws, "mid", (n,), torch.uint8, dev).zero_()) if L >= 2 else None
     raws, invs = [], []
@@ -163,10 +141,7 @@ def restricted_forward(graph, x0, n_layer, rows, ws=None):
         invs.append(inv)
         x = y
     y_top = spmm_listed(graph, rows, x)
-    z_top = torch.empty_like(y_top)
-    inv_top = torch.empty(T, dtype=torch.float32, device=x0.device)
-    _lib.check(_lib.load().tagrec_rownorm_fwd_f32(_lib.ptr(y_top), _lib.ptr(z_top), D, _lib.ptr(inv_top), T, D, _lib.stream_ptr()),
-               "rownorm_fwd")
+    z_top, inv_top = rowops.rownorm_fwd(y_top)
     out_b = x0.index_select(0, rows) * s
     for y, inv in zip(raws, invs):
         out_b.addcmul_(y.index_select(0, rows), inv.index_select(0, rows)[:, None], value=s)
@@ -185,15 +160,13 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
     s = 1.0 / (L + 1)
     T = rows.numel()
     dev = d_out_b.device
-    lib = _lib.load()
     tflag = step_buffer(ws, "tflag", (n,), torch.uint8, dev).zero_()
     tflag.index_fill_(0, rows, 1)
     dz = step_buffer(ws, "dz", (n, D), torch.float32, dev)              # d loss / d out, valid on the batch rows only
     dz.index_fill_(0, rows, 0.0)
     dz.index_add_(0, rows, d_out_b)
     g_top = torch.empty(T, D, dtype=torch.float32, device=dev)
-    _lib.check(lib.tagrec_rownorm_bwd_f32(_lib.ptr(y_top), _lib.ptr(inv_top), _lib.ptr(d_out_b), D, s, _lib.ptr(g_top), 0, T, D,
-                                          _lib.stream_ptr()), "rownorm_bwd")
+    rowops.rownorm_bwd(y_top, inv_top, d_out_b, s, g_top)
     g = step_buffer(ws, "g_top", (n, D), torch.float32, dev)             # G^L: valid on the batch rows only (flags = tflag)
     g.index_fill_(0, rows, 0.0)
     g.index_add_(0, rows, g_top)
@@ -211,10 +184,7 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
         # a masked hop wrote the rows of `mid` only: its flags must always be honoured; a full hop wrote every row
         g, flags, count = gn, fo, (None if masked else cnt)
     if fused is not None:             # (table, optimizer): the last hop applies Adam to the table, no gradient is written
-        table, opt = fused
-        m, v, step = opt.fused_state(table)
-        graph_t.spmm_axpy_adam(g, flags, count, dz, s, tflag, table.data, m, v, opt.lr, opt.betas, opt.eps, step, opt.fused_dev(table))
-        opt.fused_commit(table)
+        fused_last_hop(graph_t, fused, g, flags, count, dz, s, tflag)
         return None
     g0 = torch.empty(n, D, dtype=torch.float32, device=dev)              # (handed to the optimizer: not a workspace buffer)
     graph_t.spmm_axpy_sparse(g, flags, count, dz, s, g0, b_flags=tflag)
@@ -248,23 +218,16 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.ws = ws
         B, D = trip.shape[0], x0.shape[1]
         n = x0.shape[0]
-        lib = _lib.load()
-        coef = torch.empty(B, dtype=torch.float32, device=x0.device)
-        partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=x0.device)
-        res = torch.empty(2, dtype=torch.float32, device=x0.device)
-        ctx.n_user, ctx.n_item, ctx.reg_active, ctx.trip, ctx.coef, ctx.graph = n_user, n_item, reg_active, trip, coef, graph
+        ctx.n_user, ctx.n_item, ctx.reg_active, ctx.trip, ctx.graph = n_user, n_item, reg_active, trip, graph
         # the loss reads `out` at the batch rows only: users, and items offset by n_user
-        rows = torch.cat([trip[:, 0], trip[:, 1] + n_user, trip[:, 2] + n_user]) if restrict else None
+        rows = rowops.batch_rows(trip, n_user) if restrict else None
         ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
                            and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
         if ctx.compact:
             out_b, ctx.state = restricted_forward(graph, x0, n_layer, rows, ctx.ws)
             ego_b = x0.index_select(0, rows)
-            ar = torch.arange(B, device=x0.device)
-            ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
-            _lib.check(lib.tagrec_bpr_fwd_f32(_lib.ptr(out_b[:B]), _lib.ptr(out_b[B:]), D, D, _lib.ptr(ego_b[:B]), _lib.ptr(ego_b[B:]),
-                                              D, D, _lib.ptr(ctrip), B, loss_kind, _lib.ptr(coef), _lib.ptr(partials),
-                                              _lib.ptr(res), _lib.stream_ptr()), "bpr_fwd")
+            ctrip = rowops.compact_triplets(B, x0.device)
+            res, ctx.coef = rowops.bpr_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip, loss_kind)
             ctx.rows, ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.shape = rows, out_b, ego_b, ctrip, x0.shape
             return res
         ctx.masks = {}
@@ -272,29 +235,19 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.drops, ctx.seed = drops, seed
         U, I = out[:n_user], out[n_user:n_user + n_item]
         Ue, Ie = x0[:n_user], x0[n_user:n_user + n_item]
-        _lib.check(lib.tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), D, D, _lib.ptr(Ue), _lib.ptr(Ie), D, D,
-                                          _lib.ptr(trip), B, loss_kind, _lib.ptr(coef), _lib.ptr(partials),
-                                          _lib.ptr(res), _lib.stream_ptr()), "bpr_fwd")
+        res, ctx.coef = rowops.bpr_fwd(U, I, Ue, Ie, trip, loss_kind)
         ctx.raws, ctx.invs = raws, invs
         ctx.out, ctx.x0 = out, x0
         return res
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
-        lib = _lib.load()
-        null = _lib.c_void_p(0)
         if ctx.compact:
             out_b, ego_b, ctrip, rows = ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.rows
             B, D = ctrip.shape[0], out_b.shape[1]
             d_b = torch.zeros(2, 3 * B, D, dtype=torch.float32, device=out_b.device)   # d / d out_b, d / d ego_b
-            reg = ctx.reg_active
-            _lib.check(lib.tagrec_bpr_bwd_f32(_lib.ptr(out_b[:B]), _lib.ptr(out_b[B:]), D, D,
-                                              _lib.ptr(ego_b[:B]) if reg else null, _lib.ptr(ego_b[B:]) if reg else null,
-                                              D if reg else 0, D if reg else 0, _lib.ptr(ctrip), B, _lib.ptr(ctx.coef), _lib.ptr(g), 1.0,
-                                              _lib.ptr(d_b[0][:B]), _lib.ptr(d_b[0][B:]),
-                                              _lib.ptr(d_b[1][:B]) if reg else null, _lib.ptr(d_b[1][B:]) if reg else null,
-                                              _lib.stream_ptr()), "bpr_bwd")
+            Ue, Ie, dUe, dIe = (ego_b[:B], ego_b[B:], d_b[1][:B], d_b[1][B:]) if ctx.reg_active else (None,) * 4
+            rowops.bpr_bwd(out_b[:B], out_b[B:], Ue, Ie, ctrip, ctx.coef, g, d_b[0][:B], d_b[0][B:], dUe, dIe)
             fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
             g0 = restricted_backward(ctx.graph.transpose(), rows, d_b[0], ctx.state, ctx.shape, fused, ctx.ws)
             if ctx.reg_active:
@@ -304,29 +257,23 @@ class _PropagateBprLoss(torch.autograd.Function):
                 ctx.ws.release(ctx.token)
             return g0, None, None, None, None, None, None, None, None, None, None, None, None
         out, x0, trip = ctx.out, ctx.x0, ctx.trip
-        nu, ni, D, B = ctx.n_user, ctx.n_item, x0.shape[1], trip.shape[0]
+        nu, ni = ctx.n_user, ctx.n_item
         d_out = torch.zeros_like(out)
         U, I = out[:nu], out[nu:nu + ni]
-        _lib.check(lib.tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), D, D, null, null, 0, 0, _lib.ptr(trip), B,
-                                          _lib.ptr(ctx.coef), _lib.ptr(g), 1.0,
-                                          _lib.ptr(d_out[:nu]), _lib.ptr(d_out[nu:nu + ni]), null, null,
-                                          _lib.stream_ptr()), "bpr_bwd")
+        rowops.bpr_bwd(U, I, None, None, trip, ctx.coef, g, d_out[:nu], d_out[nu:nu + ni], None, None)
         fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active and len(ctx.raws) >= 1) else None
         g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
         # L2 term on the ego rows: added after the propagation hop has written g0
         if ctx.reg_active:
             Ue, Ie = x0[:nu], x0[nu:nu + ni]
-            _lib.check(lib.tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), D, D, _lib.ptr(Ue), _lib.ptr(Ie), D, D,
-                                              _lib.ptr(trip), B, _lib.ptr(ctx.coef), _lib.ptr(g), 1.0,
-                                              null, null, _lib.ptr(g0[:nu]), _lib.ptr(g0[nu:nu + ni]),
-                                              _lib.stream_ptr()), "bpr_bwd(reg)")
+            rowops.bpr_bwd(U, I, Ue, Ie, trip, ctx.coef, g, None, None, g0[:nu], g0[nu:nu + ni], "bpr_bwd(reg)")
         ctx.raws = ctx.invs = ctx.out = None
         if ctx.ws is not None:
             ctx.ws.release(ctx.token)
         return g0, None, None, None, None, None, None, None, None, None, None, None, None
 
 
-class LightGCN(TableModel):
+class LightGCN(FusedStepModel):
     def __init__(self, data, args=None, config=None, graph=None):
         super().__init__()
         self._config(config if config is not None else _GLOBAL_CFG)
@@ -354,26 +301,9 @@ class LightGCN(TableModel):
     def _fused_ok(self):
         return isinstance(self.norm_adj, Graph)
 
-    fused_capturable = True        # Adam(capturable=True).fuse_into(model): the fused update advances its counter on the device
-
-    def set_fused_optimizer(self, opt):
-        """`Adam.fuse_into(model)`: the compact restricted step (reg == 0) applies the table's Adam update in the epilogue of
-        its last backward product; every other path hands the optimizer a gradient as usual.  None switches it off."""
-        self._fused_opt = opt
-
-    def _drops(self):
-        """(per-layer drop rates, seed of this forward pass) when message dropout is active, else (None, 0).  The
-        seed advances with every training-mode forward pass; masks are functions of (seed, layer, element)."""
-        drops = [float(p) for p in self.message_drop_list[:self.num_layer]]
-        if not (self.training and any(p > 0 for p in drops)):
-            return None, 0
-        if self.dim_latent % 4 or self.dim_latent > 256 or self.dim_latent & (self.dim_latent - 1) or self.dim_latent < 8:
+    def _check_drop_width(self):
+        if self.dim_latent not in VEC_WIDTHS:
             raise _lib.TagrecError("LightGCN: fused message dropout needs dim_latent in {8,16,...,256}")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.TagrecError("LightGCN: message dropout draws a new seed on the host every step and cannot be captured "
-                                   "in a HIP graph")
-        self._drop_calls = getattr(self, "_drop_calls", 0) + 1
-        return drops + [0.0] * (self.num_layer - len(drops)), (int(self.drop_seed) << 24) + self._drop_calls
 
     def _graph(self):
         return H.node_drop(self.norm_adj, self.node_drop, self.training)

@@ -15,10 +15,12 @@ formed on the device, dW = dW', db = column sums of dW'.
 import torch
 import torch.nn as nn
 
-from . import _lib, help as H
-from .base import TableModel
+from . import _lib, help as H, rowops
+from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
+from .base import layer_seed as _layer_seed
 from .config import CFG as _GLOBAL_CFG
 from .graph import Graph, creat_adj
+from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
 
@@ -65,27 +67,19 @@ def dense_backward(dxp, nei, x, w1p, w2p, norm=None, row_mask=None, dz_flags=Non
 RESTRICT_FORWARD = True     # loss(): form the top two layers' neighbour sums only on the rows the batch's loss depends on
 
 
-def _layer_seed(seed, k):
-    return (int(seed) * 64 + k) & 0xFFFFFFFFFFFFFFFF
-
-
-def _drop_renorm(xp, inv, z_slot, ldz, p, seed, rows=None):
+def _drop_renorm(xp, inv, z_slot, p, seed, rows=None):
     """Message dropout of a layer's output (ngcf.py:85) behind the fused dense kernel: Xp <- mask(seed) Xp / (1 - p) with the
     library's counter-based mask, then the slot of the concatenated output and the inverse norms are recomputed from it
     (two element-wise passes; the MFMA kernels stay in use).  rows: xp holds these rows of the layer output; the mask is
     the full output's, keyed by node id (one mask per node however often a row list names it)."""
     H.message_drop(xp, p, seed, out=xp, rows=rows)
-    n, d = xp.shape
-    _lib.check(_lib.load().tagrec_rownorm_fwd_f32(_lib.ptr(xp), _lib.ptr(z_slot), ldz, _lib.ptr(inv), n, d, _lib.stream_ptr()),
-               "rownorm_fwd")
+    rowops.rownorm_fwd(xp, z_slot, inv)
 
 
-def _dxp_through_dropout(dx_next, xp, inv, dz, ldz, p, seed, rows=None):
+def _dxp_through_dropout(dx_next, xp, inv, dz, p, seed, rows=None):
     """d loss / d (pre-dropout Xp) = mask / (1 - p) * (dx_next + normalize-backward(Xp_dropped, inv, dz))."""
-    n, d = xp.shape
     g = torch.zeros_like(xp) if dx_next is None else dx_next.contiguous().clone()
-    _lib.check(_lib.load().tagrec_rownorm_bwd_f32(_lib.ptr(xp), _lib.ptr(inv), _lib.ptr(dz), ldz, 1.0, _lib.ptr(g), 1, n, d,
-                                                  _lib.stream_ptr()), "rownorm_bwd")
+    rowops.rownorm_bwd(xp, inv, dz, 1.0, g, accumulate=True)
     return H.message_drop(g, p, seed, out=g, rows=rows)
 
 
@@ -103,7 +97,7 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
     L = len(wps)
     masks = {}
     if (loss_rows is not None and L >= 1 and loss_rows.numel() * 16 <= n and graph.shape[0] == graph.shape[1]
-            and all(d in (8, 16, 32, 64, 128, 256) for d in dims[:-1])):
+            and all(d in VEC_WIDTHS for d in dims[:-1])):
         top = torch.zeros(n, dtype=torch.uint8, device=x0.device)
         top.index_fill_(0, loss_rows, 1)
         masks[L - 1] = top
@@ -126,7 +120,7 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
             dense_forward(nc, xc, w1p, w2p, xpc, invc, zc, d)
             pk = drops[k] if drops else 0.0
             if pk > 0:                      # the node's mask (keyed by node id): every slot of a repeated node is identical
-                _drop_renorm(xpc, invc, zc, d, pk, _layer_seed(seed, k), rows)
+                _drop_renorm(xpc, invc, zc, pk, _layer_seed(seed, k), rows)
             out[:, off:off + d].index_copy_(0, rows, zc)          # the other rows of this slot are never read
             saved.append(("rows", (rows, first), masks[k], masks.get(k - 1), xc, nc, xpc, invc, w1p, w2p, pk, _layer_seed(seed, k)))
             break
@@ -135,7 +129,7 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
         dense_forward(nei, x, w1p, w2p, xp, inv, out[:, off:], dtot)
         pk = drops[k] if drops else 0.0
         if pk > 0:
-            _drop_renorm(xp, inv, out[:, off:], dtot, pk, _layer_seed(seed, k))
+            _drop_renorm(xp, inv, out[:, off:], pk, _layer_seed(seed, k))
         saved.append((x, nei, xp, inv, w1p, w2p, masks.get(k), bool(masks), pk, _layer_seed(seed, k)))
         x, off = xp, off + dims[k + 1]
     return out, saved
@@ -144,7 +138,6 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
 def propagate_backward(graph_t, d_out, saved, dims):
     """d_out [N, sum(dims)] -> (d_x0, [(dW1', dW2')] per layer)."""
     n, dtot = d_out.shape
-    lib = _lib.load()
     offs = [0]
     for d in dims:
         offs.append(offs[-1] + d)
@@ -156,7 +149,7 @@ def propagate_backward(graph_t, d_out, saved, dims):
             d = dims[k + 1]
             dzc = d_out[:, offs[k + 1]:offs[k + 1] + d].index_select(0, rows) * first[:, None]     # one slot per node
             if pk > 0:
-                d_nei_c, d_xd_c, dw1, dw2 = dense_backward(_dxp_through_dropout(None, xpc, invc, dzc, d, pk, sk, rows), nc, xc, w1p, w2p)
+                d_nei_c, d_xd_c, dw1, dw2 = dense_backward(_dxp_through_dropout(None, xpc, invc, dzc, pk, sk, rows), nc, xc, w1p, w2p)
             else:
                 d_nei_c, d_xd_c, dw1, dw2 = dense_backward(None, nc, xc, w1p, w2p, norm=(xpc, invc, dzc, d))
             dws[k] = (dw1, dw2)
@@ -174,13 +167,13 @@ def propagate_backward(graph_t, d_out, saved, dims):
         # d Xp = (what layer k+1 sent back) + normalize-backward of this layer's concat slot, formed inside the kernel
         # (with message dropout: formed outside, masked, and handed to the kernel as dXp)
         if pk > 0:
-            d_nei, d_xd, dw1, dw2 = dense_backward(_dxp_through_dropout(dx_next, xp, inv, d_out[:, offs[k + 1]:], dtot, pk, sk),
+            d_nei, d_xd, dw1, dw2 = dense_backward(_dxp_through_dropout(dx_next, xp, inv, d_out[:, offs[k + 1]:], pk, sk),
                                                    nei, x, w1p, w2p)
         else:
             d_nei, d_xd, dw1, dw2 = dense_backward(dx_next, nei, x, w1p, w2p, norm=(xp, inv, d_out[:, offs[k + 1]:], dtot))
         dws[k] = (dw1, dw2)
         dx = torch.empty_like(x)
-        if restricted and x.shape[1] in (8, 16, 32, 64, 128, 256):
+        if restricted and x.shape[1] in VEC_WIDTHS:
             # restricted forward: where d_nei can be non-zero is known without looking at it.  The layer computed on a
             # row mask receives gradient on that mask only (the slot's dz lives on the batch rows, the layer above sends
             # back onto `reach` = this mask): the mask serves as the row flags.  Below that nearly every row is reached
@@ -189,26 +182,16 @@ def propagate_backward(graph_t, d_out, saved, dims):
                 graph_t.spmm_axpy_sparse(d_nei, mask_k, None, d_xd, 1.0, dx)
             else:
                 graph_t.spmm_axpy(d_nei, d_xd, 1.0, dx)
-        elif x.shape[1] in (8, 16, 32, 64, 128, 256):
+        elif x.shape[1] in VEC_WIDTHS:
             # d_nei is non-zero on the rows the batch gradient has reached so far (the batch rows in the last layer,
             # their neighbours one layer down): the product does not fetch the rows flagged zero (same result)
-            flags = torch.empty(n, dtype=torch.uint8, device=x.device)
-            count = torch.zeros(1, dtype=torch.int32, device=x.device)
-            _lib.check(lib.tagrec_row_flags_f32(_lib.ptr(d_nei), n, x.shape[1], _lib.ptr(flags), _lib.ptr(count),
-                                                _lib.stream_ptr()), "row_flags")
+            flags, count = rowops.row_flags(d_nei)
             graph_t.spmm_axpy_sparse(d_nei, flags, count, d_xd, 1.0, dx)
         else:
             graph_t.spmm_axpy(d_nei, d_xd, 1.0, dx)
         dx_next = dx
     d0 = d_out[:, :dims[0]]
     return (dx_next + d0) if dx_next is not None else d0.contiguous(), dws
-
-
-def _scatter_rows(n, rows, compact):
-    """[n, D] tensor that holds sum of compact[j] over rows[j] == r at the listed rows and is UNWRITTEN elsewhere."""
-    t = torch.empty(n, compact.shape[1], dtype=torch.float32, device=compact.device)
-    t.index_fill_(0, rows, 0.0)
-    return t.index_add_(0, rows, compact)
 
 
 def restricted_forward(graph, x0, wps, dims, rows):
@@ -220,7 +203,6 @@ def restricted_forward(graph, x0, wps, dims, rows):
     the mask.  A node named by several batch slots is computed once per slot: every backward map is linear in the
     slot's upstream gradient, so summing the slots' results (index_add) equals using the summed gradient.
     Returns (out_b [T, sum(dims)], state for `restricted_backward`)."""
-    from .lightgcn import spmm_listed
     L, n = len(wps), x0.shape[0]
     mid = graph.mark_rows(rows, torch.zeros(n, dtype=torch.uint8, device=x0.device)) if L >= 2 else None
     saved, x = [], x0
@@ -240,7 +222,7 @@ def restricted_forward(graph, x0, wps, dims, rows):
     w1p, w2p = wps[L - 1]
     d = dims[L]
     T = rows.numel()
-    nc = spmm_listed(graph, rows, x)
+    nc = graph.spmm_listed(rows, x)
     xc = x.index_select(0, rows)
     xpc = torch.empty(T, d, dtype=torch.float32, device=x0.device)
     invc = torch.empty(T, dtype=torch.float32, device=x0.device)
@@ -279,11 +261,7 @@ def restricted_backward(graph_t, rows, d_b, state, dims, n, fused=None):
         the batch rows and is folded into the addend first) -- or, with a fused optimizer, Adam applied in its epilogue."""
         addend.index_add_(0, rows, d_b[:, :dims[0]])
         if fused is not None:
-            table, opt = fused
-            m_, v_, step = opt.fused_state(table)
-            graph_t.spmm_axpy_adam(g_in, in_flags, None, addend, 1.0, b_flags, table.data, m_, v_, opt.lr, opt.betas, opt.eps, step,
-                                   opt.fused_dev(table))
-            opt.fused_commit(table)
+            fused_last_hop(graph_t, fused, g_in, in_flags, None, addend, 1.0, b_flags)
             return None
         out = torch.empty(n, dims[0], dtype=torch.float32, device=dev)
         if in_flags is None and b_flags is None:
@@ -349,30 +327,20 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         wps = _wps([m.detach() for m in mats])
         B, n = trip.shape[0], x0.shape[0]
-        rows = torch.cat([trip[:, 0], trip[:, 1] + n_user, trip[:, 2] + n_user]) if RESTRICT_FORWARD else None
-        coef = torch.empty(B, dtype=torch.float32, device=x0.device)
-        partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=x0.device)
-        res = torch.empty(2, dtype=torch.float32, device=x0.device)
-        ctx.graph, ctx.dims, ctx.trip, ctx.coef, ctx.nu, ctx.ni = graph, dims, trip, coef, n_user, n_item
+        rows = rowops.batch_rows(trip, n_user) if RESTRICT_FORWARD else None
+        ctx.graph, ctx.dims, ctx.trip, ctx.nu, ctx.ni = graph, dims, trip, n_user, n_item
         ctx.compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
                            and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
         if ctx.compact:
             out_b, ctx.state = restricted_forward(graph, x0, wps, dims, rows)
-            dtot = out_b.shape[1]
-            ar = torch.arange(B, device=x0.device)
-            ctrip = torch.stack([ar, ar, ar + B], dim=1).contiguous()
+            ctrip = rowops.compact_triplets(B, x0.device)
             U, I = out_b[:B], out_b[B:]
-            _lib.check(_lib.load().tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot, dtot,
-                                                      _lib.ptr(ctrip), B, loss_kind, _lib.ptr(coef), _lib.ptr(partials),
-                                                      _lib.ptr(res), _lib.stream_ptr()), "bpr_fwd")
+            res, ctx.coef = rowops.bpr_fwd(U, I, U, I, ctrip, loss_kind)
             ctx.rows, ctx.out_b, ctx.ctrip, ctx.n = rows, out_b, ctrip, n
             return res
         out, saved = propagate_forward(graph, x0, wps, dims, rows, drops, seed)
-        dtot = out.shape[1]
         U, I = out[:n_user], out[n_user:n_user + n_item]
-        _lib.check(_lib.load().tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot,
-                                                  dtot, _lib.ptr(trip), B, loss_kind, _lib.ptr(coef),
-                                                  _lib.ptr(partials), _lib.ptr(res), _lib.stream_ptr()), "bpr_fwd")
+        res, ctx.coef = rowops.bpr_fwd(U, I, U, I, trip, loss_kind)
         ctx.saved, ctx.out = saved, out
         return res
 
@@ -380,31 +348,24 @@ class _PropagateBprLoss(torch.autograd.Function):
     def backward(ctx, g):
         if ctx.compact:
             out_b, ctrip = ctx.out_b, ctx.ctrip
-            B, dtot = ctrip.shape[0], out_b.shape[1]
+            B = ctrip.shape[0]
             d_b = torch.zeros_like(out_b)
             U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
-            _lib.check(_lib.load().tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot, dtot,
-                                                      _lib.ptr(ctrip), B, _lib.ptr(ctx.coef), _lib.ptr(g.contiguous()), 1.0,
-                                                      _lib.ptr(dU), _lib.ptr(dI), _lib.ptr(dU), _lib.ptr(dI), _lib.stream_ptr()),
-                       "bpr_bwd")
+            rowops.bpr_bwd(U, I, U, I, ctrip, ctx.coef, g, dU, dI, dU, dI)
             d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused)
             ctx.state = ctx.out_b = None
             return (None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
         out, trip, nu, ni = ctx.out, ctx.trip, ctx.nu, ctx.ni
-        dtot = out.shape[1]
         d_out = torch.zeros_like(out)
         U, I = out[:nu], out[nu:nu + ni]
         dU, dI = d_out[:nu], d_out[nu:nu + ni]
-        _lib.check(_lib.load().tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot,
-                                                  dtot, _lib.ptr(trip), trip.shape[0], _lib.ptr(ctx.coef),
-                                                  _lib.ptr(g.contiguous()), 1.0, _lib.ptr(dU), _lib.ptr(dI),
-                                                  _lib.ptr(dU), _lib.ptr(dI), _lib.stream_ptr()), "bpr_bwd")
+        rowops.bpr_bwd(U, I, U, I, trip, ctx.coef, g, dU, dI, dU, dI)
         d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
         ctx.saved = ctx.out = None
         return (None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
 
 
-class NGCF(TableModel):
+class NGCF(FusedStepModel):
     def __init__(self, data, args=None, config=None, graph=None):
         super().__init__()
         self._config(config if config is not None else _GLOBAL_CFG)
@@ -438,29 +399,12 @@ class NGCF(TableModel):
     def _mats(self):
         return [self.mat[f"{n}_{k}"] for k in range(self.num_layer) for n in ("W1", "b1", "W2", "b2")]
 
-    fused_capturable = True
-
-    def set_fused_optimizer(self, opt):
-        """`Adam.fuse_into(model)`: the compact restricted step applies the TABLE's Adam update in the epilogue of the product
-        that lands on it (W / b keep ordinary gradients); every other path hands over a table gradient as usual."""
-        self._fused_opt = opt
+    _drop_rates = tuple        # `_drops` hands the rates to the autograd nodes as a tuple, like `dims`
 
     def _fused_ok(self):
         dl = self.dim_layer_list
         dims_ok = all(d in (16, 32, 64, 128) for d in dl)
         return isinstance(self.norm_adj, Graph) and dims_ok
-
-    def _drops(self):
-        """(per-layer drop rates, seed of this forward pass) when message dropout is active, else (None, 0): the counter-
-        based masks of the library (a function of seed, layer and element), a new seed per training-mode pass."""
-        drops = [float(p) for p in self.message_drop_list[:self.num_layer]]
-        if not (self.training and any(p > 0 for p in drops)):
-            return None, 0
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.TagrecError("NGCF: message dropout draws a new seed on the host every step and cannot be captured in a "
-                                   "HIP graph")
-        self._drop_calls = getattr(self, "_drop_calls", 0) + 1
-        return tuple(drops + [0.0] * (self.num_layer - len(drops))), (int(getattr(self, "drop_seed", 2020)) << 24) + self._drop_calls
 
     def _propagate(self):
         if self.agg_type != "bi_agg":

@@ -8,7 +8,7 @@ before they become edge values (dgcf.py:93, disengcn.py:37), so gradients only e
 operand; the backward of a routed product is the routed product with the transposed weights (`permute`)."""
 import torch
 
-from . import _lib
+from . import _lib, rowops
 from .graph import Graph
 
 
@@ -87,10 +87,7 @@ class RoutingGraph:
         inv = new(n_out, K, dtype=torch.float32, device=self.device) if normed else None
         flags = count = None
         if sparse_x:
-            flags = torch.empty(x.shape[0], dtype=torch.uint8, device=self.device)
-            count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            _lib.check(_lib.load().tagrec_row_flags_f32(_lib.ptr(x), x.shape[0], D, _lib.ptr(flags), _lib.ptr(count),
-                                                        _lib.stream_ptr()), "row_flags")
+            flags, count = rowops.row_flags(x)
         name = "route_spmm" if (row_mask is None and not sparse_x) else "route_spmm_restricted"     # timing key
         self.graph._call(name, _lib.load().tagrec_route_spmm_ex_f32, g.handle, _lib.ptr(w), K, _lib.ptr(x),
                          _lib.ptr(post), _lib.ptr(self_add), _lib.ptr(b), float(b_scale), _lib.ptr(y), _lib.ptr(yn),

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 from torch.utils.checkpoint import checkpoint
 
-from . import _lib, help as H
+from . import _lib, help as H, rowops
 from . import plan as PL
 from . import tgcn_step as TS
 from .config import CFG as _GLOBAL_CFG
@@ -105,12 +105,7 @@ def _pull_compact(idxc, attnc, doc, dh, n_dst):
 
 def _active_rows(d_out):
     """Indices of the rows of d_out [n, D] that hold a non-zero (one pass: tagrec_row_flags_f32 + nonzero)."""
-    n, D = d_out.shape
-    flags = torch.empty(n, dtype=torch.uint8, device=d_out.device)
-    count = torch.zeros(1, dtype=torch.int32, device=d_out.device)
-    _lib.check(_lib.load().tagrec_row_flags_f32(_lib.ptr(d_out), n, D, _lib.ptr(flags), _lib.ptr(count), _lib.stream_ptr()),
-               "row_flags")
-    return torch.nonzero(flags).flatten()
+    return torch.nonzero(rowops.row_flags(d_out)[0]).flatten()
 
 
 def sum_n(tensors, out=None):

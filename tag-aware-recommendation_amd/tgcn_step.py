@@ -27,7 +27,7 @@ Same loss and gradients as the all-rows pass (`TGCN.forward()` + triplet loss + 
 """
 import torch
 
-from . import _lib, help as H, plan as PL, proj as PJ
+from . import _lib, help as H, plan as PL, proj as PJ, rowops
 
 MARKS = None      # tools/c4_host_timeline.py sets a list: (name, host time, HIP event) at a few points of the step
 
@@ -308,23 +308,16 @@ def step_forward(model, batch, embs, ew, layers_ps, training_drop):
             xr = Od[t].index_select(0, extra[t])
             inv = torch.empty(n_top[t], dtype=torch.float32, device=dev)
             if n_top[t]:
-                _lib.check(lib.tagrec_rownorm_fwd_f32(_lib.ptr(xr), _lib.ptr(cat[t][:, off:]), dtot, _lib.ptr(inv), n_top[t], d_out,
-                                                      _lib.stream_ptr()), "rownorm_fwd")
+                rowops.rownorm_fwd(xr, cat[t][:, off:], inv)
             norm_saved[t] = (xr, inv)
         st.update(extra=extra, norm=norm_saved, off=off, pos_out=pos_out)
         saved.append(st)
         _mark(f"forward layer {li} queued")
         off += d_out
         X, rows_in, pos_in = Od, rows_out, pos_out
-    B = batch.shape[0]
     trip = model._batch_positions(batch)
-    coef = torch.empty(B, dtype=torch.float32, device=dev)
-    partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=dev)
-    res = torch.empty(2, dtype=torch.float32, device=dev)
     U, I = cat["user"], cat["item"]
-    _lib.check(lib.tagrec_bpr_fwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(trip), B,
-                                      H.loss_kind_id(model.loss_func), _lib.ptr(coef), _lib.ptr(partials), _lib.ptr(res),
-                                      _lib.stream_ptr()), "bpr_fwd")
+    res, coef = rowops.bpr_fwd(U, I, U, I, trip, H.loss_kind_id(model.loss_func))
     return res, {"saved": saved, "cat": cat, "trip": trip, "coef": coef, "top": top, "dims": dims, "sizes": sizes,
                  "seed": seed}
 
@@ -332,16 +325,11 @@ def step_forward(model, batch, embs, ew, layers_ps, training_drop):
 def step_backward(model, g, state, n_weight):
     """Gradients of (embed.user, embed.item, embed.tag, embed.weight, 21 parameters per layer)."""
     from . import tgcn as TG
-    lib = _lib.load()
     saved, cat, trip, coef, top, dims = (state[k] for k in ("saved", "cat", "trip", "coef", "top", "dims"))
     dev = trip.device
-    dtot = sum(dims)
-    B = trip.shape[0]
     d_cat = {t: torch.zeros_like(cat[t]) for t in cat}
     U, I, dU, dI = cat["user"], cat["item"], d_cat["user"], d_cat["item"]
-    _lib.check(lib.tagrec_bpr_bwd_f32(_lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(U), _lib.ptr(I), dtot, dtot, _lib.ptr(trip), B,
-                                      _lib.ptr(coef), _lib.ptr(g.contiguous()), 1.0, _lib.ptr(dU), _lib.ptr(dI), _lib.ptr(dU),
-                                      _lib.ptr(dI), _lib.stream_ptr()), "bpr_bwd")
+    rowops.bpr_bwd(U, I, U, I, trip, coef, g, dU, dI, dU, dI)
     L = len(saved)
     # Adam.fuse_into(model): the node tables' update rides in the epilogue of the product that forms the last term of their
     # gradient (bottom layer, dQ W_2^T): no gradient tensor for them, no separate optimizer pass over the tables
@@ -366,8 +354,7 @@ def step_backward(model, g, state, n_weight):
             if m[t] and cat[t].shape[0]:
                 xr, inv = st["norm"][t]
                 dz = torch.empty_like(xr)
-                _lib.check(lib.tagrec_rownorm_bwd_f32(_lib.ptr(xr), _lib.ptr(inv), _lib.ptr(d_cat[t][:, st["off"]:]), dtot, 1.0,
-                                                      _lib.ptr(dz), 0, xr.shape[0], xr.shape[1], _lib.stream_ptr()), "rownorm_bwd")
+                rowops.rownorm_bwd(xr, inv, d_cat[t][:, st["off"]:], 1.0, dz)
                 G_all[rng[t]].index_add_(0, st["extra"][t], dz)          # (the batch rows of a type are distinct)
         if pk > 0:                                # d out = d out' mask / (1 - p), and the kernels' relu mask [out' > 0] holds the mask
             G_all.mul_(1.0 / (1.0 - pk))

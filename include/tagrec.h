@@ -183,6 +183,29 @@ int tagrec_spmm_ss_rows_f32(const tagrec_graph* g, const float* X, float* Y, flo
 int64_t tagrec_spmm_listed_workspace(int64_t n_listed, int D);
 int tagrec_spmm_listed_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
                            int D, float* ws, int64_t ws_floats, void* stream);
+/* The masked hop below the top layer of a restricted step, driven by an inverted list of the batch rows' entries instead
+ * of a walk over every masked row: G_out[j] = sum_b A[j, b] G_in[b] over the listed rows b, for the rows j of row_mask.
+ *   batch_hop_plan   : gt = the TRANSPOSE of A (A itself when A is symmetric); rows = the n_listed (<= 16384) batch rows,
+ *                      int64, may repeat (a node counts once).  Builds, on the stream and without a host read, one record
+ *                      (destination j, source b, weight) per stored entry of a listed row of gt, grouped by destination
+ *                      and ordered by ascending source inside a destination (integer atomics only; the order does not
+ *                      depend on them).  `capacity` bounds the record count (the sum of the n_listed largest row degrees
+ *                      of gt always suffices); records beyond it are dropped -- never written -- and *err |= 1; a listed
+ *                      id outside gt's rows is skipped and *err |= 2.  err is only ever set, the caller clears it.
+ *                      ws: tagrec_batch_hop_workspace(n_rows, n_listed, capacity) bytes, 256-byte aligned.
+ *   batch_hop_normbwd: tagrec_spmm_normbwd_sparse_f32(in_flags = the listed rows, in_count = NULL, row_mask) from that
+ *                      plan.  A row of row_mask is written when it has a record or its dz_flags byte is set (NULL = every
+ *                      row); the others are left untouched, G_out and out_flags alike.  Rows of A with at most 1024 stored
+ *                      entries get the bits of the masked kernel (the same fused multiply-adds in the same order); longer
+ *                      rows are summed in ascending source order as well, in fp64 rounded once, where the masked kernel
+ *                      folds chunk partials (last bits may differ; no further from the exact sum). */
+int64_t tagrec_batch_hop_workspace(int64_t n_rows, int64_t n_listed, int64_t capacity);
+int tagrec_batch_hop_plan(const tagrec_graph* gt, const int64_t* rows, int64_t n_listed, int64_t capacity, void* ws,
+                          int64_t ws_bytes, int32_t* err, void* stream);
+int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* ws, int64_t ws_bytes, int64_t n_listed, int64_t capacity,
+                                 const float* G_in, const float* X_raw, const float* inv_norm, const float* dZ,
+                                 float d_scale, float* G_out, uint8_t* out_flags, const uint8_t* row_mask,
+                                 const uint8_t* dz_flags, int D, void* stream);
 /* tagrec_spmm_normbwd_dot_f32 (column-sharded tables) on a row-sparse G_in */
 int tagrec_spmm_normbwd_dot_sparse_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
                                        const unsigned* in_count, const float* X_raw, const float* inv_norm,

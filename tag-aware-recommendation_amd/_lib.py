@@ -135,6 +135,10 @@ _SIGNATURES = {
     "tagrec_spmm_flags_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "tagrec_spmm_listed_workspace": [c_int64, c_int],
     "tagrec_spmm_listed_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p],
+    "tagrec_batch_hop_workspace": [c_int64, c_int64, c_int64],
+    "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
+    "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "tagrec_row_flags_f32": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
     "tagrec_dh_edge_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "tagrec_dh_edge_softmax_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

@@ -408,6 +408,70 @@ class Graph:
                    int(seed), _lib.ptr(g_out), _lib.ptr(out_flags), _lib.ptr(out_count), _lib.ptr(row_mask), _lib.ptr(dz_flags), D,
                    _lib.stream_ptr())
 
+    BATCH_HOP_MAX_LISTED = 16384      # what tagrec_batch_hop_plan accepts
+
+    def batch_hop_capacity(self, n_listed):
+        """Upper bound of the records `batch_hop_plan` can produce for ANY list of n_listed rows of this matrix: the sum of
+        its n_listed largest row degrees.  One host read at first use, then cached per n_listed (a step never reads)."""
+        cache = self.__dict__.setdefault("_hop_capacity", {})
+        n_listed = min(int(n_listed), self.shape[0])
+        if n_listed not in cache:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.TagrecError("batch_hop_capacity: first use reads the row degrees on the host and cannot be captured "
+                                       "in a HIP graph; run one step eagerly first")
+            deg = self.rowptr[1:] - self.rowptr[:-1]
+            cache[n_listed] = int(torch.topk(deg, n_listed).values.sum().item()) if n_listed > 0 else 0
+        return cache[n_listed]
+
+    def batch_hop_workspace(self, n_listed, capacity):
+        """Bytes of the buffer `batch_hop_plan` needs (alignment slack included)."""
+        nb = _lib.load().tagrec_batch_hop_workspace(self.shape[1], int(n_listed), int(capacity))
+        if nb <= 0:
+            raise _lib.TagrecError("batch_hop_workspace: " + _lib.load().tagrec_last_error().decode("utf-8", "replace"))
+        return nb + 256
+
+    def batch_hop_plan(self, rows, capacity, buf):
+        """The inverted list of the stored entries of `rows` (int64 node ids, may repeat) of THIS matrix, for the hop of its
+        transpose (`Graph.batch_hop_normbwd` of `self.transpose()`): records grouped by destination = column, ascending
+        source = row inside a destination.  buf: uint8 [>= batch_hop_workspace(len(rows), capacity)], owned by the caller
+        (the step workspace).  Device only; an overflow of `capacity` is reported by `batch_hop_check`."""
+        rows = rows.contiguous()
+        _lib.require_gpu_tensor(rows, torch.int64, "batch_hop_plan rows")
+        _lib.require_gpu_tensor(buf, torch.uint8, "batch_hop_plan buf")
+        if "_hop_err" not in self.__dict__:
+            self._hop_err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        off = (-buf.data_ptr()) % 256
+        nbytes = buf.numel() - off
+        self._call("batch_hop_plan", _lib.load().tagrec_batch_hop_plan, self._h, _lib.ptr(rows), rows.numel(), int(capacity),
+                   _lib.c_void_p(buf.data_ptr() + off), nbytes, _lib.ptr(self._hop_err), _lib.stream_ptr())
+        return (buf, buf.data_ptr() + off, nbytes, rows.numel(), int(capacity))
+
+    def batch_hop_check(self):
+        """Host-side check of the plans built from this matrix so far (synchronises): raises if one overflowed its capacity
+        or was given a row id outside the matrix."""
+        err = self.__dict__.get("_hop_err")
+        code = int(err.item()) if err is not None else 0
+        if code:
+            err.zero_()
+            raise _lib.TagrecError(f"batch_hop_plan: {'record capacity exceeded; ' if code & 1 else ''}"
+                                   f"{'row id outside the matrix' if code & 2 else ''}")
+
+    def batch_hop_normbwd(self, plan, g_in, x_raw, inv_norm, dz, d_scale, g_out, out_flags, row_mask, dz_flags=None):
+        """`spmm_normbwd_sparse(in_flags = the plan's rows, in_count = None, row_mask = row_mask)` from the inverted list
+        `plan` (`self.transpose().batch_hop_plan(rows, ...)`).  Rows of row_mask that have no record and no dz_flags byte
+        are left untouched (g_out unwritten, out_flags as the caller zeroed it)."""
+        D = self._chk_x(g_in, self.shape[1], "batch_hop_normbwd g_in")
+        for t, nm in ((x_raw, "x_raw"), (dz, "dz"), (g_out, "g_out")):
+            if self._chk_x(t, self.shape[0], "batch_hop_normbwd " + nm) != D:
+                raise _lib.TagrecError("batch_hop_normbwd: width mismatch on " + nm)
+        _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
+        if row_mask.numel() != self.shape[0] or self.shape[0] != self.shape[1]:
+            raise _lib.TagrecError("batch_hop_normbwd: square matrix and one row_mask byte per row expected")
+        _, ptr, nbytes, n_listed, capacity = plan
+        self._call("batch_hop_normbwd", _lib.load().tagrec_batch_hop_normbwd_f32, self._h, _lib.c_void_p(ptr), nbytes, n_listed,
+                   capacity, _lib.ptr(g_in), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), _lib.ptr(g_out),
+                   _lib.ptr(out_flags), _lib.ptr(row_mask), _lib.ptr(dz_flags), D, _lib.stream_ptr())
+
     def spmm_axpy_sparse(self, g_in, in_flags, in_count, b, b_scale, g_out, row_mask=None, b_flags=None):
         """row_mask: rows whose byte is 0 are not touched (the caller knows their result and has written it).
         b_flags: rows of `b` whose byte is 0 are zero and are not read."""

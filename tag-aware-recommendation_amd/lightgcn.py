@@ -149,6 +149,26 @@ def restricted_forward(graph, x0, n_layer, rows, ws=None):
     return out_b, (raws, invs, mid, y_top, inv_top)
 
 
+# The masked hop of `restricted_backward` from an inverted list of the batch rows' entries (Graph.batch_hop_plan) instead of a
+# walk over every masked row.  False: always the masked row kernel (same values; the same bits on rows of <= 1024 entries).
+BATCH_HOP_LIST = True
+
+
+def batch_hop_plan(graph_t, rows, ws=None):
+    """The per-step plan of the list-driven masked hop of A = graph_t, or None where the masked row kernel serves better:
+    a list longer than the plan kernel takes, or a record bound -- the sum of the len(rows) largest row degrees, cached on
+    the graph -- above a quarter of the stored entries (the plan's buffers would rival the matrix)."""
+    src = graph_t.transpose()                 # its batch rows store exactly the entries of A that point at a batch row
+    T = rows.numel()
+    if not BATCH_HOP_LIST or T < 1 or T > Graph.BATCH_HOP_MAX_LISTED or src.shape[0] != src.shape[1]:
+        return None
+    cap = src.batch_hop_capacity(T)
+    if cap < 1 or cap > src.nnz // 4:
+        return None
+    buf = step_buffer(ws, "hop_plan", (src.batch_hop_workspace(T, cap),), torch.uint8, rows.device)
+    return src.batch_hop_plan(rows, cap, buf)
+
+
 def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=None):
     """Gradient w.r.t. x0 of `restricted_forward` given d_out_b [T, D] = d loss / d out_b.  The chain starts on the batch
     rows (compact), lands on their neighbours (row-masked hop: G is non-zero there only) and spreads from there; every
@@ -171,6 +191,7 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
     g.index_fill_(0, rows, 0.0)
     g.index_add_(0, rows, g_top)
     flags, count = tflag, None                                           # count None: the flags are always consulted
+    plan = batch_hop_plan(graph_t, rows, ws) if L >= 2 else None
     for k in range(L - 2, -1, -1):
         masked = k == L - 2
         gn = step_buffer(ws, f"g{k & 1}", (n, D), torch.float32, dev)
@@ -178,8 +199,11 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
         if masked:
             fo.zero_()
         cnt = step_buffer(ws, f"cnt{k & 1}", (1,), torch.int32, dev).zero_()
-        graph_t.spmm_normbwd_sparse(g, flags, count, raws[k], invs[k], dz, s, gn, fo, cnt, row_mask=mid if masked else None,
-                                    dz_flags=tflag)
+        if masked and plan is not None:   # rows of `mid` without a record or a dz term stay unwritten, their flag zero
+            graph_t.batch_hop_normbwd(plan, g, raws[k], invs[k], dz, s, gn, fo, mid, tflag)
+        else:
+            graph_t.spmm_normbwd_sparse(g, flags, count, raws[k], invs[k], dz, s, gn, fo, cnt, row_mask=mid if masked else None,
+                                        dz_flags=tflag)
         raws[k] = invs[k] = None          # last use: the 4 N D bytes go back to the allocator before the next hop allocates
         # a masked hop wrote the rows of `mid` only: its flags must always be honoured; a full hop wrote every row
         g, flags, count = gn, fo, (None if masked else cnt)
@@ -300,6 +324,11 @@ class LightGCN(FusedStepModel):
 
     def _fused_ok(self):
         return isinstance(self.norm_adj, Graph)
+
+    def train(self, mode=True):
+        if isinstance(getattr(self, "norm_adj", None), Graph):     # the host-side check of the steps' device-built hop plans
+            self.norm_adj.batch_hop_check()
+        return super().train(mode)
 
     def _check_drop_width(self):
         if self.dim_latent not in VEC_WIDTHS:

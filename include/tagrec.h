@@ -643,6 +643,18 @@ int64_t tagrec_masked_colsum_workspace(int D);
 int tagrec_masked_colsum_f32(const float* dOut, const float* out, int64_t n_rows, int D, float* result, float* workspace,
                              int64_t workspace_floats, void* stream);
 
+/* ---- distance-correlation loss between factor slices (model/help/loss.py:53-80; csrc/cor.hip) ----
+ * X [n, D] (row stride ld floats, rows 16-byte aligned) is K column slices of width D / K; D in {8 .. 256}, K >= 2,
+ * K | D, D / K >= 2, n >= 2.  The distances are recomputed from LDS tiles in every pass: nothing n x n is stored.
+ *   fwd: loss[1] and, for the backward pass, rowsum [n, K] (sum_j d^f_ij), gsum [K] (their column sums) and
+ *        coef [K, 3] (d loss / d d^f_ij = coef[f][0] A^{f-1} + coef[f][1] A^f + coef[f][2] A^{f+1}); part [n, 2K] and
+ *        sums [2K] are scratch (per-row and total covariance sums).  All sums have a fixed order.
+ *   bwd: dX [n, D] (row stride lddx) = g[0] * d loss / dX; every row is written once, no atomics. */
+int tagrec_cor_fwd_f32(const float* X, int64_t ld, int64_t n, int D, int K, double* rowsum, double* gsum, double* part,
+                       double* sums, float* loss, float* coef, void* stream);
+int tagrec_cor_bwd_f32(const float* X, int64_t ld, int64_t n, int D, int K, const double* rowsum, const double* gsum,
+                       const float* coef, const float* g, float* dX, int64_t lddx, void* stream);
+
 /* ---- bandwidth probes (measured ceilings of the box next to the 8 TB/s specification) ----------------
  * a = b + s * c over n floats (stream triad; 12 bytes per element; c == NULL: copy a = b, 8 bytes per element; non_temporal
  * picks the load / store flavour), and a random whole-row gather with the access shape

@@ -169,6 +169,8 @@ _SIGNATURES = {
     "tagrec_masked_colsum_workspace": [c_int],
     "tagrec_masked_colsum_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p],
     "tagrec_row_add_at_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "tagrec_cor_fwd_f32": [c_void_p, c_int64, c_int64, c_int, c_int] + [c_void_p] * 7,
+    "tagrec_cor_bwd_f32": [c_void_p, c_int64, c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p],
     "tagrec_probe_triad_f32": [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_void_p],
     "tagrec_probe_read_f32": [c_void_p, c_int64, c_void_p, c_void_p],
     "tagrec_probe_gather_out_floats": [],

@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .cor import cor_loss
 
 
 def layer_seed(seed, k):
@@ -116,6 +117,34 @@ class TableModel(nn.Module):
 
     def _split(self, out):
         return tuple(out[a:b] for a, b in zip(self._offsets[:-1], self._offsets[1:]))
+
+    # -- the distance-correlation term of the disentangled models (DGCF, DisenGCN, DisenHAN; config key `cor_loss`)
+    use_cor_loss = False
+
+    def _loss_batch(self, batch_data):
+        """`loss`'s argument, (triplets [B, 3], cor) or the triplets alone -> (triplets int64 on the device, cor).  cor
+        ([node types, c] ids per node type, what DGCF_training_data draws) is None unless the model's `cor_loss` is on:
+        with the term off that half of the batch is ignored, as in the reference."""
+        pair = isinstance(batch_data, (tuple, list))
+        data = (batch_data[0] if pair else batch_data).to(self.device, torch.int64).contiguous()
+        if not self.use_cor_loss:
+            return data, None
+        cor = batch_data[1] if pair and len(batch_data) > 1 else None
+        n_type = 3 if self.use_tag else 2
+        if cor is None or len(cor) < n_type:
+            raise _lib.TagrecError(f"{type(self).__name__}: cor_loss=True needs a (triplets, cor) batch with ids for "
+                                   f"{n_type} node types (DGCF_training_data yields it)")
+        return data, [cor[t].to(self.device, torch.int64) for t in range(n_type)]
+
+    def _cor_rows(self, cor):
+        """Node ids (with the type offsets) of the cor sample: rows a restricted forward pass must get right too."""
+        return torch.cat([c + self._offsets[t] for t, c in enumerate(cor)])
+
+    def _cor_term(self, all_embs, cor):
+        """cor_reg * cor_loss of the propagated rows cor[0] of the users, cor[1] of the items (and cor[2] of the tags),
+        stacked along dim 0 and split into factor_k column slices (the reference's commented-out block, dgcf.py:131-143)."""
+        sample = torch.cat([all_embs[t][c] for t, c in enumerate(cor)], dim=0)
+        return self.cor_reg * cor_loss(sample, self.factor_k)
 
     def train(self, mode=True):
         self._eval_cache = None          # parameters may change once training resumes

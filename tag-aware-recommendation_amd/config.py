@@ -27,8 +27,10 @@ _PER_MODEL = {
     "tgcn": {"dim_weight": 10, "dim_atten": 32, "num_bit_conv": 32, "num_vec_conv": 8, "margin": 1,
              "transtag_batch": 512, "neighbor_k": 25, "transtag_reg": 0.0001, "mul_loss_func": "logsigmoid"},
     # utility/config.py:14-30
-    "dgcf": {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100},
-    "disengcn": {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100},
+    # cor_loss (not in the reference, whose models leave the term commented out): add cor_reg * help.cor_loss on the batch's cor rows
+    "dgcf": {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100, "cor_loss": False},
+    "disengcn": {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100,
+                 "cor_loss": False},
     # utility/config.py:54-61 -- note the default agg_type "bi_agg" switches KGAT's propagation off (kgat.py:100)
     "kgat": {"dim_relation": 64, "transe_reg": 0.0001, "transe_batch": 1024, "agg_type": "bi_agg", "mul_loss_func": "softplus"},
 }

@@ -4,6 +4,8 @@
     .forward(out_A=False)     -> tuple(user_emb, item_emb[, tag_emb]); out_A=True -> per layer, per factor, the
                                  routing weights of the last iteration as sparse tensors                (:51-68)
     .loss((batch[B,3], cor))  -> (mul_loss, reg * l2reg_loss on EGO rows)                               (:115-145)
+                                 config cor_loss=True: + cor_reg * cor_loss of the propagated cor rows   (:131-143, commented
+                                 out in the reference); off (the default) the cor half is ignored
     .predict_rating(users)    -> sigmoid(U_b I^T)                                                       (:147-152)
 
 Per layer and routing iteration the reference builds K sparse tensors and runs 3K sparse products plus two
@@ -75,6 +77,7 @@ class DGCF(TableModel):
         self.dim_k = self.dim_latent // self.factor_k
         self.reg = config["reg"]
         self.cor_reg = config.get("cor_reg", 0)
+        self.use_cor_loss = bool(config.get("cor_loss", False))
         self.loss_func = config["mul_loss_func"]
         self.use_tag = config["use_tag"]
         self.restrict_forward = bool(config.get("restrict_forward", True))
@@ -107,11 +110,15 @@ class DGCF(TableModel):
         return self._split(out)
 
     def loss(self, batch_data):
-        data = batch_data[0] if isinstance(batch_data, (tuple, list)) else batch_data       # (triplets, cor), :116
-        data = data.to(self.device, torch.int64).contiguous()
+        data, cor = self._loss_batch(batch_data)                                            # (triplets, cor), :116
         nu = self.num_list[0]
         rows = torch.cat([data[:, 0], data[:, 1] + nu, data[:, 2] + nu]) if self.restrict_forward else None
-        all_users, all_items = self.forward(loss_rows=rows)[:2]
+        if cor is not None and rows is not None:
+            rows = torch.cat([rows, self._cor_rows(cor)])
+        all_embs = self.forward(loss_rows=rows)
+        all_users, all_items = all_embs[:2]
         ego = self.embed
         loss, reg_loss = H.triplet_loss(all_users, all_items, ego[0], ego[1], data, self.loss_func)
-        return loss, self.reg * reg_loss
+        if cor is None:
+            return loss, self.reg * reg_loss
+        return loss, self.reg * reg_loss, self._cor_term(all_embs, cor)

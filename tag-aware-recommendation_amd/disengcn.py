@@ -3,6 +3,8 @@
     DisenGCN(data)            three tables (user, item, tag -- always, :51) + per layer W [K, D, D/K], b [K, 1, D/K]
     .forward()                -> tuple(user_emb, item_emb, tag_emb): the LAST layer's output only          (:90-103)
     .loss((batch[B,3], cor))  -> (mul_loss, reg * l2reg_loss on the PROPAGATED rows)                       (:105-131)
+                              config cor_loss=True: + cor_reg * cor_loss of the propagated cor rows (:116-128, commented
+                              out in the reference); off (the default) the cor half is ignored
 
 Layer (:23-46): f = normalize(LeakyReLU_0.2(x (W + b))) per factor; `iterate_k` rounds of
 p = softmax_k <new_f[head], f[tail]>;  new_f_k = normalize(f_k + A(p_k) f_k).  The K [D, D/K] projections are ONE
@@ -87,6 +89,8 @@ class DisenGCN(TableModel):
         self.iterate_k = config["iterate_k"]
         self.dim_k = self.dim_latent // self.factor_k
         self.reg = config["reg"]
+        self.cor_reg = config.get("cor_reg", 0)
+        self.use_cor_loss = bool(config.get("cor_loss", False))
         self.loss_func = config["mul_loss_func"]
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
@@ -103,10 +107,14 @@ class DisenGCN(TableModel):
         return self._split(x)
 
     def loss(self, batch_data):
-        data = batch_data[0] if isinstance(batch_data, (tuple, list)) else batch_data
-        data = data.to(self.device, torch.int64).contiguous()
+        data, cor = self._loss_batch(batch_data)
         nu = self.num_list[0]
         rows = torch.cat([data[:, 0], data[:, 1] + nu, data[:, 2] + nu]) if self.restrict_forward else None
-        all_users, all_items = self.forward(loss_rows=rows)[:2]
+        if cor is not None and rows is not None:
+            rows = torch.cat([rows, self._cor_rows(cor)])
+        all_embs = self.forward(loss_rows=rows)
+        all_users, all_items = all_embs[:2]
         loss, reg_loss = H.triplet_loss(all_users, all_items, all_users, all_items, data, self.loss_func)
-        return loss, self.reg * reg_loss
+        if cor is None:
+            return loss, self.reg * reg_loss
+        return loss, self.reg * reg_loss, self._cor_term(all_embs, cor)

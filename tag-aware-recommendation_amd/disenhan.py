@@ -3,7 +3,9 @@
     DisenHAN(data)            three tables (user, item, tag) + per layer Wtk [3, K, D, dk], at [6, K, 2 dk], W [dk, dk],
                               q_rela [6, dk]                                                              (:21-26, :146-157)
     .forward()                -> (user_emb, item_emb, tag_emb): the LAST layer's output                   (:159-179)
-    .loss((batch[B,3], cor))  -> (mul_loss, reg * l2reg_loss on the PROPAGATED rows); cor is unused       (:181-214)
+    .loss((batch[B,3], cor))  -> (mul_loss, reg * l2reg_loss on the PROPAGATED rows)                      (:181-214)
+                              config cor_loss=True: + cor_reg * cor_loss of the propagated cor rows (:200-212, commented
+                              out in the reference); off (the default) the cor half is ignored
     .predict_rating(users)    -> sigmoid(U_b I^T)                                                         (:216-222)
 
 Layer (:28-97): ego_t = slice_normalize(leaky_0.2(emb_t Wtk[t])) -- one [D, D] GEMM per node type; then two routing
@@ -31,7 +33,8 @@ COMBINE = ((0, 2), (1, 4), (3, 5))                              # relations adde
 ITERATE = 2                                                     # Layer(K, D, D, 6, 2) (:157)
 
 # utility/config.py:32-39
-_DISENHAN = {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100}
+_DISENHAN = {"mul_loss_func": "softplus", "norm_type": "plain", "factor_k": 4, "iterate_k": 2, "cor_batch": 100,
+             "cor_loss": False}
 
 
 def disenhan_config(**overrides):
@@ -248,6 +251,7 @@ class DisenHAN(TableModel):
         self.dim_k = self.dim_latent // self.factor_k
         self.reg = config["reg"]
         self.cor_reg = config["cor_reg"]
+        self.use_cor_loss = bool(config.get("cor_loss", False))
         self.loss_func = config["mul_loss_func"]
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
@@ -259,8 +263,10 @@ class DisenHAN(TableModel):
         return tuple(x)
 
     def loss(self, batch_data):
-        data = batch_data[0] if isinstance(batch_data, (tuple, list)) else batch_data
-        data = data.to(self.device, torch.int64).contiguous()
-        all_users, all_items = self.forward()[:2]
+        data, cor = self._loss_batch(batch_data)
+        all_embs = self.forward()
+        all_users, all_items = all_embs[:2]
         loss, reg_loss = H.triplet_loss(all_users, all_items, all_users, all_items, data, self.loss_func)
-        return loss, self.reg * reg_loss
+        if cor is None:
+            return loss, self.reg * reg_loss
+        return loss, self.reg * reg_loss, self._cor_term(all_embs, cor)

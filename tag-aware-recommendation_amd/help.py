@@ -6,6 +6,7 @@ argument meaning, backed by the HIP library through `torch.autograd.Function`s.
     mul_loss(u, p, n, loss_func)             loss.py:4-12
     l2reg_loss(*embs)                        loss.py:27-32
     transtag_loss / transe_loss              loss.py:35-50
+    cor_loss(factor_emb, factor_k)           loss.py:53-80   (kernels: csrc/cor.hip, host side: cor.py)
     creat_adj(...)                           adj.py:38-46   (re-exported from graph.py)
 
 Inputs must be GPU tensors; there is no CPU path.
@@ -13,6 +14,7 @@ Inputs must be GPU tensors; there is no CPU path.
 import torch
 
 from . import _lib, rowops
+from .cor import cor_loss  # noqa: F401  (the distance-correlation penalty between factor slices)
 from .graph import Graph, coalesce_device, creat_adj  # noqa: F401  (creat_adj re-exported)
 
 

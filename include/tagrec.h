@@ -183,6 +183,42 @@ int tagrec_spmm_ss_rows_f32(const tagrec_graph* g, const float* X, float* Y, flo
 int64_t tagrec_spmm_listed_workspace(int64_t n_listed, int D);
 int tagrec_spmm_listed_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
                            int D, float* ws, int64_t ws_floats, void* stream);
+/* Edge dropout (`node_drop`, model/help/adj.py:170-191, used at model/lightgcn.py:50) evaluated INSIDE the products: no
+ * dropped CSR is built, no mask is stored, nothing is sorted.  For the stored entry (i, j) of the forward matrix
+ *     key  = (uint64(i) << 32) | uint32(j);   h = mix64(seed ^ mix64(key))      (the splitmix64 finaliser of the
+ *     keep = (h >> 40) >= (unsigned)(p * 16777216.0f)                             message-dropout masks)
+ * a kept entry contributes val / (1 - p) (a true fp32 division, as the reference divides), a dropped one nothing -- its
+ * operand row is not fetched; (i, j) and (j, i) draw independently.  ed_transposed != 0: the handle holds the TRANSPOSE
+ * of the matrix the mask is defined on (the symmetric bi_norm matrix itself, or an explicit transpose), so the entry met
+ * as (row r, column c) takes the draw of (c, r): forward and backward of one step see the same dropped matrix.
+ * The `_edrop` forms take the arguments of the product they are named after plus (ed_p, ed_seed, ed_transposed) and need
+ * a vector-kernel width (D in {8, 16, 32, 64, 128, 256}, 16-byte aligned operands; anything else is TAGREC_E_UNSUPPORTED):
+ *   spmm_edrop                : tagrec_spmm_f32
+ *   spmm_norm_acc_rows_edrop  : tagrec_spmm_norm_acc_rows_f32 (row_mask NULL = every row, acc may be NULL)
+ *   spmm_normbwd_sparse_edrop : tagrec_spmm_normbwd_sparse_f32 (in_flags NULL = dense operand)
+ *   spmm_axpy_sparse_edrop    : tagrec_spmm_axpy_sparse_f32
+ *   spmm_listed_edrop         : tagrec_spmm_listed_f32
+ *   edge_drop_mask            : mask_out[e] = 1 iff stored entry e (CSR order) is kept -- for tests and for host helpers
+ *                               that materialise the dropped matrix */
+int tagrec_edge_drop_mask_u8(const tagrec_graph* g, float p, uint64_t seed, int transposed, uint8_t* mask_out, void* stream);
+int tagrec_spmm_edrop_f32(const tagrec_graph* g, const float* X, float* Y, float ed_p, uint64_t ed_seed, int ed_transposed,
+                          int D, void* stream);
+int tagrec_spmm_norm_acc_rows_edrop_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
+                                        float* acc, float acc_scale, const uint8_t* row_mask, float drop_p,
+                                        uint64_t seed, float ed_p, uint64_t ed_seed, int ed_transposed, int D, void* stream);
+int tagrec_spmm_normbwd_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                         const unsigned* in_count, const float* X_raw, const float* inv_norm,
+                                         const float* dZ, float d_scale, float drop_p, uint64_t seed, float* G_out,
+                                         uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask,
+                                         const uint8_t* dz_flags, float ed_p, uint64_t ed_seed, int ed_transposed, int D,
+                                         void* stream);
+int tagrec_spmm_axpy_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                      const unsigned* in_count, const float* B, float b_scale, float* G_out,
+                                      const uint8_t* row_mask, const uint8_t* b_flags, float ed_p, uint64_t ed_seed,
+                                      int ed_transposed, int D, void* stream);
+int tagrec_spmm_listed_edrop_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
+                                 int D, float* ws, int64_t ws_floats, float ed_p, uint64_t ed_seed, int ed_transposed,
+                                 void* stream);
 /* The masked hop below the top layer of a restricted step, driven by an inverted list of the batch rows' entries instead
  * of a walk over every masked row: G_out[j] = sum_b A[j, b] G_in[b] over the listed rows b, for the rows j of row_mask.
  *   batch_hop_plan   : gt = the TRANSPOSE of A (A itself when A is symmetric); rows = the n_listed (<= 16384) batch rows,

@@ -135,6 +135,18 @@ _SIGNATURES = {
     "tagrec_spmm_flags_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "tagrec_spmm_listed_workspace": [c_int64, c_int],
     "tagrec_spmm_listed_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p],
+    # edge dropout inside the products (adj.py:170-191): the product's own arguments + (ed_p, ed_seed, ed_transposed)
+    "tagrec_edge_drop_mask_u8": [c_void_p, c_float, ctypes.c_uint64, c_int, c_void_p, c_void_p],
+    "tagrec_spmm_edrop_f32": [c_void_p, c_void_p, c_void_p, c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
+    "tagrec_spmm_norm_acc_rows_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float,
+                                            ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
+    "tagrec_spmm_normbwd_sparse_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                             ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                             ctypes.c_uint64, c_int, c_int, c_void_p],
+    "tagrec_spmm_axpy_sparse_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                          c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
+    "tagrec_spmm_listed_edrop_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float,
+                                     ctypes.c_uint64, c_int, c_void_p],
     "tagrec_batch_hop_workspace": [c_int64, c_int64, c_int64],
     "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

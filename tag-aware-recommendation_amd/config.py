@@ -15,6 +15,7 @@ _BASE = {
     "topks": [10, 20], "lr": 0.01, "reg": 0.0, "cor_reg": 0.0,
     "epochs": 1000, "dim_latent": 64, "dim_layer_list": [64, 32, 16],
     "message_drop_list": [0.0, 0.0, 0.0], "node_drop": 0.0,
+    "node_drop_mode": "rebuild",   # "kernel": edge dropout evaluated inside the products (help.node_drop), no CSR rebuilt per step
     "seed": 2020, "cpu_core": 4, "split_adj_k": 1,
     "hip_graph": False,       # Basic_train: replay each phase's step as one captured HIP graph (train.GraphedStep)
     "all_gather": "collective",   # row-sharded models (dist.py): "direct" = one grouped send / receive pair per peer

@@ -60,6 +60,23 @@ __device__ __forceinline__ void drop4(const DropMask& m, int64_t float4_index, f
 }
 
 
+// Edge dropout (`node_drop`, /root/reference/model/help/adj.py:170-191) evaluated inside the products: whether the stored
+// entry (i, j) of the FORWARD matrix survives is a pure function of (seed, i, j), so no dropped CSR is built, no mask is
+// stored and the backward pass re-creates the forward's mask.  (i, j) and (j, i) draw independently, as the reference
+// drops COO entries one by one.  A product with the TRANSPOSE walks the row of j and meets column i: `transposed` swaps the
+// hash arguments so that it evaluates the mask of (i, j).  A kept entry contributes val / (1 - p).
+struct EdgeDrop {
+  float p;          // drop probability; 0 = nothing dropped
+  uint64_t seed;
+  int transposed;   // the walked matrix is the transpose of the one the mask is defined on
+};
+__host__ __device__ inline bool edge_kept(const EdgeDrop& d, int64_t row, int col) {
+  const uint64_t i = static_cast<uint64_t>(d.transposed ? static_cast<int64_t>(col) : row);
+  const uint32_t j = static_cast<uint32_t>(d.transposed ? row : static_cast<int64_t>(col));
+  const uint64_t h = mix64(d.seed ^ mix64((i << 32) | j));
+  return (h >> 40) >= static_cast<unsigned>(d.p * 16777216.0f);     // keep iff the 24-bit draw >= p * 2^24
+}
+
 // torch.optim.Adam's update (_single_tensor_adam: exp_avg.lerp_(grad, 1 - b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad,
 // 1 - b2); param.addcdiv_(exp_avg, sqrt(exp_avg_sq) / sqrt(bc2) + eps, -step_size)), shared by the Adam kernels (rowops.hip)
 // and the last backward hop's fused epilogue (spmm.hip).  The roundings are PINNED -- contraction off, the three fused

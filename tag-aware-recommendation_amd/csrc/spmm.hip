@@ -87,9 +87,13 @@ __device__ __forceinline__ float f4_dot(const float4& a, const float4& b) {
 
 // Sum of val[j] * X[col[j], :] over j in [start, end).  LPR = lanes per row = D/4.  On return every
 // lane holds the full sum for its float4 column (lane % LPR).
-template <int LPR, bool FLAGS = false>
+// EDROP: the range belongs to row `row` and every entry is put to the edge-dropout mask `ed` (common.h) first -- a dropped
+// entry is "not wanted" exactly like an entry whose operand row is not flagged, a kept one weighs val / (1 - p); `flags`
+// may be given on top (nullptr = every operand row is wanted).  Off, the parameter compiles to nothing.
+template <int LPR, bool FLAGS = false, bool EDROP = false>
 __device__ __forceinline__ float4 gather_rows(const GraphView& g, const float* __restrict__ X,
-                                              int64_t start, int64_t end, int lane, const uint8_t* __restrict__ flags = nullptr) {
+                                              int64_t start, int64_t end, int lane, const uint8_t* __restrict__ flags = nullptr,
+                                              int64_t row = 0, const EdgeDrop& ed = EdgeDrop{0.f, 0, 0}) {
   constexpr int NPI = kWave / LPR;  // neighbour rows per wave-instruction
   const int q = lane / LPR;
   const float4* __restrict__ Xv = reinterpret_cast<const float4*>(X) + (lane % LPR);
@@ -100,13 +104,15 @@ __device__ __forceinline__ float4 gather_rows(const GraphView& g, const float* _
     float my_val = 0.f;
     if (lane < n) {
       my_col = ld_stream(g.col + base + lane);
-      if constexpr (FLAGS) {
+      if constexpr (EDROP) {
+        if (edge_kept(ed, row, my_col) && (!flags || flags[my_col])) my_val = ld_stream(g.val + base + lane) / (1.0f - ed.p);
+      } else if constexpr (FLAGS) {
         if (flags[my_col]) my_val = ld_stream(g.val + base + lane);    // a zero weight marks "row not needed"
       } else {
         my_val = ld_stream(g.val + base + lane);
       }
     }
-    if constexpr (FLAGS) {
+    if constexpr (FLAGS || EDROP) {
       // Keep only the entries whose operand row is flagged: they move to the first lanes (order preserved) and the
       // gather loop below runs over them alone -- a batch of 64 entries with nothing flagged costs its index / flag reads
       // and nothing else.  (dest is a permutation of the 64 lanes: flagged entries first, the rest behind them.)
@@ -130,7 +136,7 @@ __device__ __forceinline__ float4 gather_rows(const GraphView& g, const float* _
         const int j = (gi + u) * NPI + q;
         const int c = __shfl(my_col, j & (kWave - 1));
         const float w = __shfl(my_val, j & (kWave - 1));
-        const bool ok = FLAGS ? (j < n && w != 0.f) : (j < n);
+        const bool ok = (FLAGS || EDROP) ? (j < n && w != 0.f) : (j < n);
         v[u] = ok ? w : 0.f;
         x[u] = ok ? Xv[static_cast<int64_t>(c) * LPR] : f4_zero();
       }
@@ -282,6 +288,38 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_kernel(Graph
   row_epilogue<LPR, EPI>(acc, r, lane, e);
 }
 
+// The edge-dropout form (gather_rows<.., EDROP>): every entry of row r is put to the mask first; a chunk wave takes its row id
+// from the chunk descriptor.  A kernel of its own, so that the p = 0 kernel above keeps its name, code and register allocation
+// (the precedent: the fused TGCN kernels).
+template <int LPR, int EPI, bool MASKED = false>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_edrop_kernel(GraphView g, const float* __restrict__ X,
+                                                                                  EpiArgs e, LongView lv, EdgeDrop ed) {
+  const int lane = threadIdx.x & (kWave - 1);
+  if (blockIdx.x < lv.chunk_blocks) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    if (c >= lv.n_chunks) return;
+    const int2 d = lv.chunk_desc[c];
+    if (d.x < 0) return;                    // unused slot of a handle created without a host read
+    const int64_t r = lv.long_rows[d.x];
+    if (MASKED && !e.row_mask[r]) return;
+    const int64_t start = g.rowptr[r] + static_cast<int64_t>(d.y) * kChunk;
+    const int64_t row_end = g.rowptr[r + 1];
+    const int64_t end = (start + kChunk < row_end) ? start + kChunk : row_end;
+    const bool sparse = e.in_flags && (!e.in_count || 5ull * (*e.in_count) < 4ull * static_cast<unsigned long long>(g.n_cols));
+    const float4 acc = gather_rows<LPR, false, true>(g, X, start, end, lane, sparse ? e.in_flags : nullptr, r, ed);
+    if (lane < LPR) reinterpret_cast<float4*>(lv.slab)[c * LPR + lane] = acc;
+    return;
+  }
+  const int64_t r = static_cast<int64_t>(blockIdx.x - lv.chunk_blocks) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (r >= g.n_rows) return;
+  if (MASKED && !e.row_mask[r]) return;
+  const int64_t start = g.rowptr[r], end = g.rowptr[r + 1];
+  if (end - start > kLongRow) return;  // chunked above, folded by spmm_finish_kernel
+  const bool sparse = e.in_flags && (!e.in_count || 5ull * (*e.in_count) < 4ull * static_cast<unsigned long long>(g.n_cols));
+  const float4 acc = gather_rows<LPR, false, true>(g, X, start, end, lane, sparse ? e.in_flags : nullptr, r, ed);
+  row_epilogue<LPR, EPI>(acc, r, lane, e);
+}
+
 // ---- masked hop with a handful of flagged operand rows: one row per LANE GROUP ------------------------------------------
 // The hop below the top layer of a restricted backward pass visits the rows of a mask (the batch rows' neighbours: ~40 % of
 // the graph at C2) and gathers only FLAGGED operand rows (the <= 3 B batch rows): a row reads its ~50 column ids and flag
@@ -384,6 +422,102 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_grouped_kern
   }
 }
 
+// the edge-dropout form of the grouped hop: an entry counts when its operand row is flagged AND the mask keeps it
+template <int LPR, int EPI>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_grouped_edrop_kernel(GraphView g, const float* __restrict__ X,
+                                                                                          EpiArgs e, LongView lv, EdgeDrop ed) {
+  static_assert(EPI == EPI_NORMBWD || EPI == EPI_AXPY, "grouped rows: the two masked backward hops");
+  static_assert(LPR <= 32, "grouped rows: at least two rows per wavefront");
+  constexpr int NPI = kWave / LPR;
+  const int lane = threadIdx.x & (kWave - 1);
+  if (blockIdx.x < lv.chunk_blocks) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    if (c >= lv.n_chunks) return;
+    const int2 d = lv.chunk_desc[c];
+    if (d.x < 0) return;
+    const int64_t r = lv.long_rows[d.x];
+    if (!e.row_mask[r]) return;
+    const int64_t start = g.rowptr[r] + static_cast<int64_t>(d.y) * kChunk;
+    const int64_t row_end = g.rowptr[r + 1];
+    const int64_t end = (start + kChunk < row_end) ? start + kChunk : row_end;
+    const float4 acc = gather_rows<LPR, false, true>(g, X, start, end, lane, e.in_flags, r, ed);
+    if (lane < LPR) reinterpret_cast<float4*>(lv.slab)[c * LPR + lane] = acc;
+    return;
+  }
+  const int q = lane / LPR, c = lane % LPR;
+  const int64_t wv = static_cast<int64_t>(blockIdx.x - lv.chunk_blocks) * kWavesPerBlock + (threadIdx.x >> 6);
+  const int64_t r = wv * NPI + q;
+  bool valid = r < g.n_rows && e.row_mask[r];
+  int64_t start = 0;
+  int len = 0;
+  if (valid) {
+    start = g.rowptr[r];
+    const int64_t deg = g.rowptr[r + 1] - start;
+    if (deg > kLongRow) valid = false;          // chunked above, folded by spmm_finish_kernel
+    else len = static_cast<int>(deg);
+  }
+  int maxlen = len;
+#pragma unroll
+  for (int m = LPR; m < kWave; m <<= 1) maxlen = max(maxlen, __shfl_xor(maxlen, m));
+  const float4* __restrict__ Xv = reinterpret_cast<const float4*>(X) + c;
+  float4 acc = f4_zero();
+  for (int base = 0; base < maxlen; base += LPR) {
+    const int n = len - base;                    // entries of this group's row in the batch (may be <= 0)
+    int my_col = 0;
+    float my_val = 0.f;
+    if (c < n) {
+      my_col = ld_stream(g.col + start + base + c);
+      if (e.in_flags[my_col] && edge_kept(ed, r, my_col)) my_val = ld_stream(g.val + start + base + c) / (1.0f - ed.p);   // 0: "not needed"
+    }
+    const unsigned long long m = __ballot(my_val != 0.f);
+    unsigned gm = static_cast<unsigned>((m >> (q * LPR)) & ((1ull << LPR) - 1ull));   // the group's flagged entries
+    int maxcnt = __popc(gm);
+#pragma unroll
+    for (int mm = LPR; mm < kWave; mm <<= 1) maxcnt = max(maxcnt, __shfl_xor(maxcnt, mm));
+    for (int t = 0; t < maxcnt; t += 2) {
+      float4 x[2];
+      float v[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const bool ok = gm != 0u;
+        const int bit = ok ? __ffs(static_cast<int>(gm)) - 1 : 0;
+        gm &= gm - 1u;                                                            // (0 stays 0)
+        const int col = __shfl(my_col, q * LPR + bit);
+        const float w = __shfl(my_val, q * LPR + bit);
+        v[u] = ok ? w : 0.f;
+        x[u] = ok ? Xv[static_cast<int64_t>(col) * LPR] : f4_zero();
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) f4_fma(acc, v[u], x[u]);
+    }
+  }
+  if (!valid) return;                            // (whole lane groups leave: the group reductions below stay inside a group)
+  const int64_t off = r * LPR + c;
+  float4 o = acc;
+  if constexpr (EPI == EPI_NORMBWD) {
+    if (!e.b_flags || e.b_flags[r]) {
+      const float4 xr = ld_stream(reinterpret_cast<const float4*>(e.Xraw) + off);
+      float4 dz = ld_stream(reinterpret_cast<const float4*>(e.B) + off);
+      dz.x *= e.s; dz.y *= e.s; dz.z *= e.s; dz.w *= e.s;
+      const float4 gz = normalize_bwd<LPR>(xr, e.inv_norm[r], dz);
+      o = make_float4(acc.x + gz.x, acc.y + gz.y, acc.z + gz.z, acc.w + gz.w);
+    }
+    drop4(e.drop, off, o.x, o.y, o.z, o.w);
+    st_stream(reinterpret_cast<float4*>(e.Y) + off, o);
+    if (e.out_flags) {
+      const float nz = group_sum<LPR>((o.x != 0.f || o.y != 0.f || o.z != 0.f || o.w != 0.f) ? 1.f : 0.f);
+      if (c == 0) e.out_flags[r] = nz != 0.f;
+    }
+  } else {
+    if (!(e.b_flags && !e.b_flags[r])) {
+      const float4 b = ld_stream(reinterpret_cast<const float4*>(e.B) + off);
+      o = make_float4(fmaf(e.s, b.x, acc.x), fmaf(e.s, b.y, acc.y), fmaf(e.s, b.z, acc.z), fmaf(e.s, b.w, acc.w));
+    }
+    st_stream(reinterpret_cast<float4*>(e.Y) + off, o);
+  }
+}
+
+// (the fold of the long-row chunks sees partial sums only: one kernel serves the plain and the edge-dropout products)
 template <int LPR, int EPI, bool MASKED = false>
 __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_finish_kernel(GraphView g,
                                                                               const int32_t* __restrict__ long_rows,
@@ -556,6 +690,52 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_listed_kernel(Gra
     }
     out[lane] = a;
   }
+}
+
+// the edge-dropout form: each of the 32 x 4 ranges knows its listed row
+template <int LPR>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_listed_edrop_kernel(GraphView g, const int64_t* __restrict__ rows,
+                                                                                    const float* __restrict__ X, float* __restrict__ ws,
+                                                                                    EdgeDrop ed) {
+  __shared__ float4 part[kWavesPerBlock][LPR];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  const int64_t k = blockIdx.x / kListedSplits;
+  const int sp = blockIdx.x % kListedSplits;
+  const int64_t r = rows[k];
+  const int64_t start = g.rowptr[r], end = g.rowptr[r + 1];
+  const int64_t per_split = ((end - start + kListedSplits * kWave - 1) / (kListedSplits * kWave)) * kWave;
+  const int64_t b0 = (start + sp * per_split < end) ? start + sp * per_split : end;
+  const int64_t b1 = (b0 + per_split < end) ? b0 + per_split : end;
+  float4* out = reinterpret_cast<float4*>(ws) + (k * kListedSplits + sp) * LPR;
+  if (b0 >= b1) {                                   // nothing in this range (short rows use the first ranges only)
+    if (threadIdx.x < LPR) out[threadIdx.x] = f4_zero();
+    return;
+  }
+  const int64_t per = ((b1 - b0 + kWavesPerBlock * kWave - 1) / (kWavesPerBlock * kWave)) * kWave;
+  const int64_t s0 = (b0 + wave * per < b1) ? b0 + wave * per : b1;
+  const int64_t s1 = (s0 + per < b1) ? s0 + per : b1;
+  const float4 acc = gather_rows<LPR, false, true>(g, X, s0, s1, lane, nullptr, r, ed);
+  if (lane < LPR) part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && lane < LPR) {
+    float4 a = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < kWavesPerBlock; ++w) {
+      const float4 b = part[w][lane];
+      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    out[lane] = a;
+  }
+}
+
+// keep byte of every stored entry under the edge-dropout mask, in CSR order (one wavefront per row): what the products above
+// evaluate on the fly, for tests and for the host helper that materialises the dropped matrix
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void edge_drop_mask_kernel(GraphView g, EdgeDrop ed, uint8_t* __restrict__ mask) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (r >= g.n_rows) return;
+  const int64_t end = g.rowptr[r + 1];
+  for (int64_t j = g.rowptr[r] + lane; j < end; j += kWave) mask[j] = edge_kept(ed, r, g.col[j]) ? 1 : 0;
 }
 
 template <int LPR>
@@ -1089,8 +1269,32 @@ int tagrec::ensure_slab(const tagrec_graph* g, int D) {
 
 namespace {
 
+// the edge-dropout forms of launch_vec's three gather kernels (ed != nullptr); the fold of the long rows is shared
 template <int LPR, int EPI>
-int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStream_t s) {
+int launch_vec_edrop(const GraphView& gv, const float* X, const EpiArgs& e, const LongView& lv, unsigned blocks, int threads,
+                     const EdgeDrop& ed, hipStream_t s) {
+  if constexpr (EPI == EPI_NONE || EPI == EPI_NORM_ACC || EPI == EPI_NORMBWD || EPI == EPI_AXPY) {
+    if (!e.row_mask) {
+      spmm_rows_edrop_kernel<LPR, EPI><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
+      return TAGREC_OK;
+    }
+    if constexpr ((EPI == EPI_NORMBWD || EPI == EPI_AXPY) && LPR <= 32) {
+      if (e.in_flags && !e.in_count) {
+        constexpr int rows_per_block = kWavesPerBlock * (kWave / LPR);
+        const unsigned gblocks = static_cast<unsigned>((gv.n_rows + rows_per_block - 1) / rows_per_block);
+        spmm_rows_grouped_edrop_kernel<LPR, EPI><<<gblocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
+        return TAGREC_OK;
+      }
+    }
+    spmm_rows_edrop_kernel<LPR, EPI, true><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
+    return TAGREC_OK;
+  } else {
+    return fail(TAGREC_E_UNSUPPORTED, "edge dropout: not available for this product");
+  }
+}
+
+template <int LPR, int EPI>
+int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStream_t s, const EdgeDrop* ed = nullptr) {
   const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
   const int threads = kWavesPerBlock * kWave;
   const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
@@ -1100,6 +1304,18 @@ int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStrea
     if (rc != TAGREC_OK) return rc;
     lv.slab = g->slab;
     lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
+  }
+  if (ed) {
+    int rc = launch_vec_edrop<LPR, EPI>(gv, X, e, lv, blocks, threads, *ed, s);
+    if (rc != TAGREC_OK) return rc;
+    TAGREC_LAUNCH_CHECK();
+    if (g->n_long > 0) {
+      const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
+      if (e.row_mask) spmm_finish_kernel<LPR, EPI, true><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
+      else spmm_finish_kernel<LPR, EPI><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
+      TAGREC_LAUNCH_CHECK();
+    }
+    return TAGREC_OK;
   }
   if (e.row_mask) {                       // rows whose mask byte is 0 are left alone (a separate instantiation)
     constexpr bool kGroupable = (EPI == EPI_NORMBWD || EPI == EPI_AXPY) && LPR <= 32;
@@ -1133,7 +1349,8 @@ int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStrea
 }
 
 template <int EPI>
-int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, void* stream, const char* who) {
+int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, void* stream, const char* who,
+                const EdgeDrop* ed = nullptr) {
   TAGREC_REQUIRE(g != nullptr, std::string(who) + ": null graph handle");
   TAGREC_REQUIRE(X != nullptr && e.Y != nullptr, std::string(who) + ": null X or output");
   TAGREC_REQUIRE(D >= 1, std::string(who) + ": D must be >= 1");
@@ -1147,15 +1364,18 @@ int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, 
   if (e.drop.p > 0.f && !vec_ok) return fail(TAGREC_E_INVALID, std::string(who) + ": dropout needs 16-byte aligned rows");
   if (vec_ok) {
     switch (D) {
-      case 8: return launch_vec<2, EPI>(g, X, e, s);
-      case 16: return launch_vec<4, EPI>(g, X, e, s);
-      case 32: return launch_vec<8, EPI>(g, X, e, s);
-      case 64: return launch_vec<16, EPI>(g, X, e, s);
-      case 128: return launch_vec<32, EPI>(g, X, e, s);
-      case 256: return launch_vec<64, EPI>(g, X, e, s);
+      case 8: return launch_vec<2, EPI>(g, X, e, s, ed);
+      case 16: return launch_vec<4, EPI>(g, X, e, s, ed);
+      case 32: return launch_vec<8, EPI>(g, X, e, s, ed);
+      case 64: return launch_vec<16, EPI>(g, X, e, s, ed);
+      case 128: return launch_vec<32, EPI>(g, X, e, s, ed);
+      case 256: return launch_vec<64, EPI>(g, X, e, s, ed);
       default: break;
     }
   }
+  if (ed)       // the scalar kernel knows no edge mask: it would multiply by the un-dropped matrix
+    return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": edge dropout needs the vector kernels (D in {8,...,256}, every operand "
+                                                         "16-byte aligned)");
   if (EPI == EPI_NORM_ACC && !e.accum)
     return fail(TAGREC_E_INVALID, std::string(who) + ": acc may be NULL only with the vector kernels (D in {8,...,256}, aligned rows)");
   if (e.adam.p)       // the scalar kernel stores the raw gradient into e.Y == p and never touches m / v
@@ -1422,6 +1642,119 @@ extern "C" int tagrec_spmm_ss_rows_f32(const tagrec_graph* g, const float* X, fl
   TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_ss_rows: D must be 8 .. 256, a power of two");
   EpiArgs e{Y, ss, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask};
   return launch_spmm<EPI_SS>(g, X, e, D, stream, "spmm_ss_rows");
+}
+
+// ---- edge dropout inside the products (`node_drop`, /root/reference/model/help/adj.py:170-191; EdgeDrop in common.h) -------
+// The `_edrop` form of a product multiplies by the matrix whose entry (i, j) is dropped with probability ed_p under ed_seed and
+// otherwise scaled by 1 / (1 - ed_p); ed_transposed != 0: the handle holds the transpose of the matrix the mask is defined on.
+namespace {
+int edrop_args(const char* who, float ed_p, int D) {
+  TAGREC_REQUIRE(ed_p >= 0.f && ed_p < 1.f, std::string(who) + ": edge-drop p must be in [0, 1)");
+  if (!(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256))
+    return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": edge dropout needs a vector-kernel width (D must be 8 .. 256, a power of two)");
+  return TAGREC_OK;
+}
+}  // namespace
+
+extern "C" int tagrec_edge_drop_mask_u8(const tagrec_graph* g, float p, uint64_t seed, int transposed, uint8_t* mask_out,
+                                        void* stream) {
+  TAGREC_REQUIRE(g != nullptr && (g->nnz == 0 || mask_out != nullptr), "edge_drop_mask: null pointer");
+  TAGREC_REQUIRE(p >= 0.f && p < 1.f, "edge_drop_mask: p must be in [0, 1)");
+  if (g->n_rows == 0 || g->nnz == 0) return TAGREC_OK;
+  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
+  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
+  edge_drop_mask_kernel<<<blocks, kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(gv, EdgeDrop{p, seed, transposed != 0},
+                                                                                                mask_out);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_spmm_edrop_f32(const tagrec_graph* g, const float* X, float* Y, float ed_p, uint64_t ed_seed,
+                                     int ed_transposed, int D, void* stream) {
+  int rc = edrop_args("spmm_edrop", ed_p, D);
+  if (rc != TAGREC_OK) return rc;
+  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
+  EpiArgs e{Y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  return launch_spmm<EPI_NONE>(g, X, e, D, stream, "spmm_edrop", &ed);
+}
+
+extern "C" int tagrec_spmm_norm_acc_rows_edrop_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
+                                                   float* acc, float acc_scale, const uint8_t* row_mask, float drop_p,
+                                                   uint64_t seed, float ed_p, uint64_t ed_seed, int ed_transposed, int D,
+                                                   void* stream) {
+  TAGREC_REQUIRE(inv_norm != nullptr, "spmm_norm_acc_rows_edrop: null inv_norm");
+  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_norm_acc_rows_edrop: p must be in [0, 1)");
+  int rc = edrop_args("spmm_norm_acc_rows_edrop", ed_p, D);
+  if (rc != TAGREC_OK) return rc;
+  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
+  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{drop_p, seed}, nullptr, nullptr, nullptr, row_mask, nullptr};
+  return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, "spmm_norm_acc_rows_edrop", &ed);
+}
+
+extern "C" int tagrec_spmm_normbwd_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                                    const unsigned* in_count, const float* X_raw, const float* inv_norm,
+                                                    const float* dZ, float d_scale, float drop_p, uint64_t seed, float* G_out,
+                                                    uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask,
+                                                    const uint8_t* dz_flags, float ed_p, uint64_t ed_seed, int ed_transposed,
+                                                    int D, void* stream) {
+  TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, "spmm_normbwd_sparse_edrop: null X_raw, inv_norm or dZ");
+  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_normbwd_sparse_edrop: in_count without in_flags");
+  TAGREC_REQUIRE((out_flags == nullptr) == (out_count == nullptr), "spmm_normbwd_sparse_edrop: out_flags and out_count go together");
+  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_normbwd_sparse_edrop: p must be in [0, 1)");
+  int rc = edrop_args("spmm_normbwd_sparse_edrop", ed_p, D);
+  if (rc != TAGREC_OK) return rc;
+  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
+  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, nullptr, d_scale, DropMask{drop_p, seed}, in_flags, in_count, out_flags, row_mask, dz_flags};
+  rc = launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, "spmm_normbwd_sparse_edrop", &ed);
+  if (rc != TAGREC_OK || !out_flags) return rc;
+  return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tagrec_spmm_axpy_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                                 const unsigned* in_count, const float* B, float b_scale, float* G_out,
+                                                 const uint8_t* row_mask, const uint8_t* b_flags, float ed_p, uint64_t ed_seed,
+                                                 int ed_transposed, int D, void* stream) {
+  TAGREC_REQUIRE(B != nullptr, "spmm_axpy_sparse_edrop: null B");
+  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_axpy_sparse_edrop: in_count without in_flags");
+  int rc = edrop_args("spmm_axpy_sparse_edrop", ed_p, D);
+  if (rc != TAGREC_OK) return rc;
+  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
+  EpiArgs e{G_out, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, in_flags, in_count, nullptr, row_mask, b_flags};
+  return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy_sparse_edrop", &ed);
+}
+
+extern "C" int tagrec_spmm_listed_edrop_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
+                                            int D, float* ws, int64_t ws_floats, float ed_p, uint64_t ed_seed, int ed_transposed,
+                                            void* stream) {
+  TAGREC_REQUIRE(g != nullptr && X != nullptr && Y != nullptr && (n_listed == 0 || rows != nullptr), "spmm_listed_edrop: null pointer");
+  TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), "spmm_listed_edrop: bad row count");
+  TAGREC_REQUIRE(aligned16(X) && aligned16(Y) && aligned16(ws), "spmm_listed_edrop: rows must be 16-byte aligned");
+  TAGREC_REQUIRE(n_listed == 0 || (ws != nullptr && ws_floats >= tagrec_spmm_listed_workspace(n_listed, D)),
+                 "spmm_listed_edrop: workspace smaller than tagrec_spmm_listed_workspace(n_listed, D)");
+  int rc = edrop_args("spmm_listed_edrop", ed_p, D);
+  if (rc != TAGREC_OK) return rc;
+  if (n_listed == 0) return TAGREC_OK;
+  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
+  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned blocks = static_cast<unsigned>(n_listed * kListedSplits);
+  const int threads = kWavesPerBlock * kWave;
+#define LISTED(L)                                                                                   \
+  spmm_listed_edrop_kernel<L><<<blocks, threads, 0, s>>>(gv, rows, X, ws, ed);                      \
+  TAGREC_LAUNCH_CHECK();                                                                            \
+  spmm_listed_fold_kernel<L><<<static_cast<unsigned>((n_listed * L + 255) / 256), 256, 0, s>>>(ws, Y, n_listed); \
+  break
+  switch (D) {
+    case 8: LISTED(2);
+    case 16: LISTED(4);
+    case 32: LISTED(8);
+    case 64: LISTED(16);
+    case 128: LISTED(32);
+    default: LISTED(64);
+  }
+#undef LISTED
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
 }
 
 // ---- TGCN attention backward pulls (see attn_pull_da_kernel / attn_pull_dq_kernel) ------------------------------------

@@ -518,6 +518,145 @@ class Graph:
         self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_f32, self._h, _lib.ptr(g_in), _lib.ptr(b),
                    float(b_scale), _lib.ptr(g_out), D, _lib.stream_ptr())
 
+    # -- edge dropout inside the products ----------------------------------------------------------
+    def edge_drop(self, p, seed):
+        """This matrix under edge dropout (`node_drop`, adj.py:170-191) as a light view: same handle, no copy, nothing
+        sorted -- the products evaluate the mask of (p, seed) entry by entry (csrc/common.h EdgeDrop)."""
+        return EdgeDropView(self, p, seed, False)
+
+    def edge_drop_mask(self, p, seed, transposed=False):
+        """uint8 [nnz]: 1 where the stored entry (CSR order) survives the mask of (p, seed)."""
+        mask = torch.empty(self.nnz, dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.load().tagrec_edge_drop_mask_u8(self._h, float(p), int(seed) & _U64, int(bool(transposed)), _lib.ptr(mask),
+                                                        _lib.stream_ptr()), "edge_drop_mask")
+        return mask
+
+    def edge_drop_materialise(self, p, seed):
+        """An ordinary `Graph` of the entries `edge_drop(p, seed)` keeps, each divided by 1 - p (fp32, as the kernels
+        divide).  For tests and tools: the training step never builds it."""
+        keep = self.edge_drop_mask(p, seed).bool()
+        deg = self.rowptr[1:] - self.rowptr[:-1]
+        rows = torch.repeat_interleave(torch.arange(self.shape[0], device=self.device), deg)[keep]
+        rowptr = torch.zeros(self.shape[0] + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(torch.bincount(rows, minlength=self.shape[0]), 0, out=rowptr[1:])
+        scale = 1.0 - torch.tensor(float(p), dtype=torch.float32, device=self.device)
+        return Graph(rowptr, self.col[keep].contiguous(), (self.val[keep] / scale).contiguous(), self.shape)
+
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+class EdgeDropView:
+    """`graph` with every stored entry (i, j) dropped with probability p under `seed` and the survivors divided by 1 - p
+    -- `node_drop` of the reference (adj.py:170-191) -- without a second CSR: the view carries (p, seed, transposed) to the
+    edge-dropout forms of the products, which evaluate the mask as they walk the rows.  It has the method surface the
+    LightGCN step uses.  `transpose()` is the same view with `transposed` flipped: on the symmetric bi_norm matrix the
+    structure is its own transpose and only the order of the hash arguments differs; on any other matrix the explicit
+    transposed handle is walked with the flag set.  Vector-kernel widths only (rowops.VEC_WIDTHS)."""
+
+    def __init__(self, graph, p, seed, transposed):
+        if not isinstance(graph, Graph):
+            raise _lib.TagrecError("edge_drop: one Graph expected (row folds -- split_adj_k > 1 -- are not covered in kernel mode)")
+        if not 0.0 <= float(p) < 1.0:
+            raise _lib.TagrecError("edge_drop: p must be in [0, 1)")
+        self.base, self.p, self.seed, self.transposed = graph, float(p), int(seed) & _U64, bool(transposed)
+        self.shape = graph.shape
+        self.symmetric = False            # (i, j) and (j, i) draw independently: the dropped matrix is not symmetric
+
+    nnz = property(lambda self: self.base.nnz)                # stored entries walked, not entries kept
+    device = property(lambda self: self.base.device)
+    handle = property(lambda self: self.base.handle)
+
+    def transpose(self):
+        return EdgeDropView(self.base.transpose(), self.p, self.seed, not self.transposed)
+
+    def materialise(self):
+        """The ordinary Graph this view multiplies by (tests / tools)."""
+        if not self.transposed:
+            return self.base.edge_drop_materialise(self.p, self.seed)
+        return self.base.transpose().edge_drop_materialise(self.p, self.seed).transpose()
+
+    def mark_rows(self, rows, flags):
+        """`Graph.mark_rows` of the UN-dropped matrix: a superset of the rows the dropped top layer reads, which keeps a
+        restricted step exact (the extra rows are computed and never read with a non-zero gradient)."""
+        return self.base.mark_rows(rows, flags)
+
+    def _ed(self):
+        return float(self.p), self.seed, int(self.transposed)
+
+    def _width(self, X, rows, name):
+        D = self.base._chk_x(X, rows, name)
+        if D not in (8, 16, 32, 64, 128, 256):
+            raise _lib.TagrecError(f"{name}: edge dropout in the kernels needs a width in {{8, 16, ..., 256}}, got {D} "
+                                   "(the generic scalar kernel has no edge-drop form)")
+        return D
+
+    def spmm(self, X, out=None):
+        D = self._width(X, self.shape[1], "spmm X")
+        if out is None:
+            out = torch.empty(self.shape[0], D, dtype=torch.float32, device=X.device)
+        self.base._chk_x(out, self.shape[0], "spmm out")
+        self.base._call("spmm", _lib.load().tagrec_spmm_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(out), *self._ed(), D,
+                        _lib.stream_ptr())
+        return out
+
+    def spmm_norm_acc(self, X, y_raw, inv_norm, acc, acc_scale, drop_p=0.0, seed=0):
+        self.spmm_norm_acc_rows(X, y_raw, inv_norm, acc, acc_scale, None, drop_p, seed)
+
+    def spmm_norm_acc_rows(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, drop_p=0.0, seed=0):
+        D = self._width(X, self.shape[1], "spmm_norm_acc X")
+        self.base._call("spmm_norm_acc_rows" if row_mask is not None else "spmm_norm_acc",
+                        _lib.load().tagrec_spmm_norm_acc_rows_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(y_raw), _lib.ptr(inv_norm),
+                        _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), *self._ed(), D,
+                        _lib.stream_ptr())
+
+    def spmm_listed(self, rows, X, out=None):
+        rows = rows.contiguous()
+        lib = _lib.load()
+        D = self._width(X, self.shape[1], "spmm_listed X")
+        if out is None:
+            out = torch.empty(rows.numel(), D, dtype=torch.float32, device=X.device)
+        ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), D)
+        ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
+        self.base._call("spmm_listed", lib.tagrec_spmm_listed_edrop_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
+                        _lib.ptr(out), D, _lib.ptr(ws), ws_n, *self._ed(), _lib.stream_ptr())
+        return out
+
+    def spmm_normbwd(self, g_in, x_raw, inv_norm, dz, d_scale, g_out, drop_p=0.0, seed=0):
+        self.spmm_normbwd_sparse(g_in, None, None, x_raw, inv_norm, dz, d_scale, g_out, None, None, drop_p, seed)
+
+    def spmm_normbwd_sparse(self, g_in, in_flags, in_count, x_raw, inv_norm, dz, d_scale, g_out, out_flags, out_count,
+                            drop_p=0.0, seed=0, row_mask=None, dz_flags=None):
+        D = self._width(g_in, self.shape[1], "spmm_normbwd g_in")
+        for t, nm in ((x_raw, "x_raw"), (dz, "dz"), (g_out, "g_out")):
+            if self.base._chk_x(t, self.shape[0], "spmm_normbwd " + nm) != D:
+                raise _lib.TagrecError("spmm_normbwd: width mismatch on " + nm)
+        if row_mask is not None:
+            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
+            if row_mask.numel() != self.shape[0]:
+                raise _lib.TagrecError("spmm_normbwd_sparse: row_mask must have one byte per row")
+        self.base._call("spmm_normbwd_rows" if row_mask is not None else "spmm_normbwd",
+                        _lib.load().tagrec_spmm_normbwd_sparse_edrop_f32, self.handle, _lib.ptr(g_in), _lib.ptr(in_flags),
+                        _lib.ptr(in_count), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p),
+                        int(seed), _lib.ptr(g_out), _lib.ptr(out_flags), _lib.ptr(out_count), _lib.ptr(row_mask),
+                        _lib.ptr(dz_flags), *self._ed(), D, _lib.stream_ptr())
+
+    def spmm_axpy(self, g_in, b, b_scale, g_out):
+        self.spmm_axpy_sparse(g_in, None, None, b, b_scale, g_out)
+
+    def spmm_axpy_sparse(self, g_in, in_flags, in_count, b, b_scale, g_out, row_mask=None, b_flags=None):
+        D = self._width(g_in, self.shape[1], "spmm_axpy g_in")
+        for t, nm in ((b, "b"), (g_out, "g_out")):
+            if self.base._chk_x(t, self.shape[0], "spmm_axpy " + nm) != D:
+                raise _lib.TagrecError("spmm_axpy: width mismatch on " + nm)
+        if row_mask is not None:
+            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
+            if row_mask.numel() != self.shape[0]:
+                raise _lib.TagrecError("spmm_axpy_sparse: row_mask must have one byte per row")
+        self.base._call("spmm_axpy_rows" if row_mask is not None else "spmm_axpy", _lib.load().tagrec_spmm_axpy_sparse_edrop_f32,
+                        self.handle, _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(b), float(b_scale),
+                        _lib.ptr(g_out), _lib.ptr(row_mask), _lib.ptr(b_flags), *self._ed(), D, _lib.stream_ptr())
+
 
 def creat_adj(data, use_tag, norm_type, split_adj_k, device):
     """Same name, arguments and result convention as the reference's `creat_adj`

@@ -218,14 +218,30 @@ def message_dropout(x, p, seed):
     return x if p <= 0 else _MessageDrop.apply(x, float(p), int(seed))
 
 
-def node_drop(graph, keep_prob, training=False):
+NODE_DROP_MODES = ("rebuild", "kernel")
+
+
+def node_drop(graph, keep_prob, training=False, mode="rebuild", seed=None):
     """Edge dropout (adj.py:170-191).  As in the reference the argument called
     `keep_prob` is the DROP rate: an edge survives iff int(rand + (1-drop)) != 0
     and survivors are divided by (1-drop).  The mask is drawn on the GPU (the
-    reference draws it on the CPU), so parity is statistical."""
+    reference draws it on the CPU), so parity is statistical.
+
+    mode="rebuild": a torch.rand mask and a new CSR (and, for the backward pass, its transpose) per call.
+    mode="kernel":  `Graph.edge_drop(keep_prob, seed)` -- a view of the same CSR whose products evaluate a counter-based
+                    mask of (seed, row, column) as they go; nothing is rebuilt or sorted.  One Graph only (no row folds),
+                    vector-kernel widths only; `seed` is required (one per training forward pass)."""
+    if mode not in NODE_DROP_MODES:
+        raise _lib.TagrecError(f"node_drop: unknown mode {mode!r} (have {NODE_DROP_MODES})")
     assert 0 <= keep_prob < 1
     if keep_prob == 0 or not training:
         return graph
+    if mode == "kernel":
+        if isinstance(graph, (list, tuple)):
+            raise _lib.TagrecError("node_drop(mode='kernel'): row folds (split_adj_k > 1) are not covered; use mode='rebuild'")
+        if seed is None:
+            raise _lib.TagrecError("node_drop(mode='kernel'): a seed is required")
+        return graph.edge_drop(keep_prob, seed)
     keep = 1.0 - keep_prob
 
     def drop(g):

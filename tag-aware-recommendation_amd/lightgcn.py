@@ -18,7 +18,7 @@ from . import _lib, help as H, rowops
 from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
 from .base import layer_seed as _layer_seed
 from .config import CFG as _GLOBAL_CFG
-from .graph import Graph, creat_adj
+from .graph import EdgeDropView, Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
@@ -104,6 +104,8 @@ def propagate_backward(graph_t, d_out, raws, invs, drops=None, seed=0, masks=Non
         else:
             graph_t.spmm_normbwd(g, raws[k], invs[k], d_out, s, gn, drops[k] if drops else 0.0, _layer_seed(seed, k))
         g = gn
+    if isinstance(graph_t, EdgeDropView):
+        fused = None                      # the Adam-in-epilogue hop has no edge-drop form: the optimizer gets a gradient tensor
     if fused is not None and sparse:      # (table, optimizer): Adam in the epilogue of the last hop, no gradient tensor
         fused_last_hop(graph_t, fused, g, flags[cur], counts[cur:cur + 1], d_out, s, None)
         return None
@@ -158,6 +160,8 @@ def batch_hop_plan(graph_t, rows, ws=None):
     """The per-step plan of the list-driven masked hop of A = graph_t, or None where the masked row kernel serves better:
     a list longer than the plan kernel takes, or a record bound -- the sum of the len(rows) largest row degrees, cached on
     the graph -- above a quarter of the stored entries (the plan's buffers would rival the matrix)."""
+    if isinstance(graph_t, EdgeDropView):     # edge dropout: the list-driven hop has no edge-drop form; the masked row kernel has
+        return None
     src = graph_t.transpose()                 # its batch rows store exactly the entries of A that point at a batch row
     T = rows.numel()
     if not BATCH_HOP_LIST or T < 1 or T > Graph.BATCH_HOP_MAX_LISTED or src.shape[0] != src.shape[1]:
@@ -207,6 +211,8 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
         raws[k] = invs[k] = None          # last use: the 4 N D bytes go back to the allocator before the next hop allocates
         # a masked hop wrote the rows of `mid` only: its flags must always be honoured; a full hop wrote every row
         g, flags, count = gn, fo, (None if masked else cnt)
+    if isinstance(graph_t, EdgeDropView):
+        fused = None                  # the Adam-in-epilogue hop has no edge-drop form: the optimizer gets a gradient tensor
     if fused is not None:             # (table, optimizer): the last hop applies Adam to the table, no gradient is written
         fused_last_hop(graph_t, fused, g, flags, count, dz, s, tflag)
         return None
@@ -316,6 +322,10 @@ class LightGCN(FusedStepModel):
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
         self.node_drop = config["node_drop"]
+        # "kernel": edge dropout evaluated inside the products (Graph.edge_drop) instead of a CSR rebuilt per forward pass
+        self.node_drop_mode = config.get("node_drop_mode", "rebuild")
+        if self.node_drop_mode not in H.NODE_DROP_MODES:
+            raise _lib.TagrecError(f"LightGCN: unknown node_drop_mode {self.node_drop_mode!r} (have {H.NODE_DROP_MODES})")
         self.drop_seed = config.get("seed", 2020)
         # loss(): compute the top two layers only on the rows the batch's loss depends on (propagate_forward)
         self.restrict_forward = bool(config.get("restrict_forward", True))
@@ -335,7 +345,19 @@ class LightGCN(FusedStepModel):
             raise _lib.TagrecError("LightGCN: fused message dropout needs dim_latent in {8,16,...,256}")
 
     def _graph(self):
-        return H.node_drop(self.norm_adj, self.node_drop, self.training)
+        """The adjacency of this forward pass.  Kernel-mode edge dropout draws one seed per training-mode call, advanced like
+        the message-dropout seed (`_drops`): every layer of the pass and its backward see the same dropped graph."""
+        if self.node_drop_mode != "kernel" or not self.training or self.node_drop == 0:
+            return H.node_drop(self.norm_adj, self.node_drop, self.training)
+        if not isinstance(self.norm_adj, Graph):
+            raise _lib.TagrecError("LightGCN: node_drop_mode='kernel' does not cover row folds (split_adj_k > 1)")
+        if self.dim_latent not in VEC_WIDTHS:
+            raise _lib.TagrecError("LightGCN: node_drop_mode='kernel' needs dim_latent in {8,16,...,256}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.TagrecError("LightGCN: kernel-mode node_drop draws a new seed on the host every step and cannot be "
+                                   "captured in a HIP graph")
+        self._node_drop_calls = getattr(self, "_node_drop_calls", 0) + 1
+        return H.node_drop(self.norm_adj, self.node_drop, True, "kernel", (int(self.drop_seed) << 24) + self._node_drop_calls)
 
     def _propagate(self):
         graph = self._graph()
@@ -358,9 +380,10 @@ class LightGCN(FusedStepModel):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
         if self._fused_ok():
+            graph = self._graph()                       # (first: kernel-mode edge dropout refuses a capture before any launch)
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
-            res = _PropagateBprLoss.apply(self.table, self._graph(), self.num_layer, nu, ni, batch_data,
+            res = _PropagateBprLoss.apply(self.table, graph, self.num_layer, nu, ni, batch_data,
                                           H.loss_kind_id(self.loss_func), self.reg != 0, drops, seed, self.restrict_forward,
                                           fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None)
             return res[0], self.reg * res[1]

@@ -70,8 +70,9 @@ class _TripletLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, I, Ureg, Ireg, trip, loss_kind):
-        for t, nm in ((U, "U"), (I, "I")):
-            _lib.require_gpu_tensor(t, torch.float32, "bpr " + nm)
+        for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
+            if t is not None:
+                _lib.require_gpu_tensor(t, torch.float32, "bpr " + nm)
         trip = _lib.require_gpu_tensor(trip.contiguous(), torch.int64, "bpr triplets")
         has_reg = Ureg is not None
         out, coef = rowops.bpr_fwd(U, I, Ureg, Ireg, trip, loss_kind)

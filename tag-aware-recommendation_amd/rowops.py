@@ -56,8 +56,29 @@ def row_flags(x, flags=None, count=None):
     return flags, count
 
 
-def _reg(Ureg):
-    return (0, 0) if Ureg is None else (Ureg.stride(0), Ureg.shape[1])
+def _pair_ld(what, names, A, B, grads=()):
+    """Row stride and width that the kernels index BOTH tables of a pair (U / I, Ureg / Ireg) and their gradient buffers
+    with; raises before any launch if they do not share them.  A one-row tensor fits any row stride."""
+    if A is None and B is None:
+        return 0, 0
+    if A is None or B is None:
+        raise _lib.TagrecError(f"{what}: {names[0]} / {names[1]} must both be given or both None")
+    if A.dim() != 2 or B.dim() != 2 or B.shape[1] != A.shape[1]:
+        raise _lib.TagrecError(f"{what}: {names[0]} {tuple(A.shape)} and {names[1]} {tuple(B.shape)} must be 2-d of one width")
+    ld = None
+    for nm, t in zip(names + tuple("d" + n for n in names), (A, B) + tuple(grads)):
+        if t is None:
+            continue
+        if t.dim() != 2 or t.shape[1] != A.shape[1]:
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must be 2-d of width {A.shape[1]}")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise _lib.TagrecError(f"{what}: {nm} must have unit inner stride, got {t.stride(1)}")
+        if t.shape[0] > 1:
+            if ld is not None and t.stride(0) != ld:
+                raise _lib.TagrecError(f"{what}: {nm} has row stride {t.stride(0)}, but the kernel indexes {names[0]}, {names[1]} "
+                                       f"and their gradient buffers with one row stride ({ld})")
+            ld = t.stride(0)
+    return (A.shape[1] if ld is None else ld), A.shape[1]
 
 
 def bpr_fwd(U, I, Ureg, Ireg, trip, loss_kind):
@@ -66,18 +87,21 @@ def bpr_fwd(U, I, Ureg, Ireg, trip, loss_kind):
     coef = torch.empty(B, dtype=torch.float32, device=U.device)
     partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=U.device)     # two floats per launched block
     res = torch.empty(2, dtype=torch.float32, device=U.device)
-    ldreg, dreg = _reg(Ureg)
-    check(load().tagrec_bpr_fwd_f32(ptr(U), ptr(I), U.stride(0), U.shape[1], ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
+    ld, D = _pair_ld("bpr_fwd", ("U", "I"), U, I)
+    ldreg, dreg = _pair_ld("bpr_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
+    check(load().tagrec_bpr_fwd_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
                                     loss_kind, ptr(coef), ptr(partials), ptr(res), stream_ptr()), "bpr_fwd")
     return res, coef
 
 
 def bpr_bwd(U, I, Ureg, Ireg, trip, coef, g, dU, dI, dUreg, dIreg, what="bpr_bwd"):
     """Scatter-adds the gradients of `bpr_fwd`'s two loss parts (g = their upstream gradients, two floats) into the
-    caller-zeroed dU / dI and dUreg / dIreg.  dU = dI = None: the L2 part only; Ureg = Ireg = None: no L2 part."""
-    g = g.contiguous()
-    ldreg, dreg = _reg(Ureg)
-    check(load().tagrec_bpr_bwd_f32(ptr(U), ptr(I), U.stride(0), U.shape[1], ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip),
+    caller-zeroed dU / dI and dUreg / dIreg.  dU = dI = None: the L2 part only; Ureg = Ireg = None: no L2 part; g = None: both
+    upstream gradients are 1."""
+    g = None if g is None else g.contiguous()
+    ld, D = _pair_ld(what, ("U", "I"), U, I, (dU, dI))
+    ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
+    check(load().tagrec_bpr_bwd_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip),
                                     trip.shape[0], ptr(coef), ptr(g), 1.0, ptr(dU), ptr(dI), ptr(dUreg), ptr(dIreg),
                                     stream_ptr()), what)
 
@@ -86,8 +110,9 @@ def bpr_dots(U, I, Ureg, Ireg, trip):
     """dots[b] = (u.p, u.n, 0.5 (|u|^2 + |p|^2 + |n|^2)) over the local columns of a column-sharded table -> [B, 3]."""
     B = trip.shape[0]
     dots = torch.empty(B, 3, dtype=torch.float32, device=U.device)
-    ldreg, dreg = _reg(Ureg)
-    check(load().tagrec_bpr_dots_f32(ptr(U), ptr(I), U.stride(0), U.shape[1], ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
+    ld, D = _pair_ld("bpr_dots", ("U", "I"), U, I)
+    ldreg, dreg = _pair_ld("bpr_dots", ("Ureg", "Ireg"), Ureg, Ireg)
+    check(load().tagrec_bpr_dots_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
                                      ptr(dots), stream_ptr()), "bpr_dots")
     return dots
 

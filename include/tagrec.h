@@ -242,6 +242,29 @@ int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* ws, int64_t 
                                  const float* G_in, const float* X_raw, const float* inv_norm, const float* dZ,
                                  float d_scale, float* G_out, uint8_t* out_flags, const uint8_t* row_mask,
                                  const uint8_t* dz_flags, int D, void* stream);
+/* Fixed-order scatter of compact rows into a table, dst[rows[j]] (=|+=) src[j], for a row list that repeats ids: no float
+ * atomics, the same bits on every run (config key `deterministic` of LightGCN / NGCF).
+ *   rowlist_plan : rows = n_listed int64 ids (may repeat) into a table of n rows.  Builds in ws, on the stream and without a
+ *                  host read: order (int32 [n_listed], the slots stably sorted by row id), seg_row (int32, the distinct
+ *                  rows ascending), seg_ptr (int32, segment s = order[seg_ptr[s] .. seg_ptr[s + 1])) and counts (int32
+ *                  [4]: segments, valid slots, ids outside [0, n), 0).  An id outside [0, n) is dropped from the plan and
+ *                  counted.  ws: tagrec_rowlist_workspace(n_listed, width) bytes, 256-byte aligned, width = the widest row
+ *                  the plan will scatter; part p of the plan (0 order, 1 seg_row, 2 seg_ptr, 3 counts) starts at byte
+ *                  tagrec_rowlist_plan_result(n_listed, width, p).
+ *   row_scatter_ordered : dst[seg_row[s]] = (accumulate ? dst[seg_row[s]] : 0) + sum of src[order[j]] over segment s.  src
+ *                  [n_listed, D] with row stride lds, dst [n_dst >= n, D] with row stride ldd, D <= width.  The order of
+ *                  the sum is part of the contract: ascending slot id; a segment of <= 1024 slots is one left-to-right
+ *                  fp32 chain from its first term; a longer one is cut into consecutive 1024-slot chunks, each such a
+ *                  chain, whose sums are added left to right.  dst is touched once per segment (a store, or one fp32 add
+ *                  of the finished sum); rows outside the list are not touched.  D in {8, .., 256} with 16-byte aligned
+ *                  rows takes D / 4 lanes x 16 bytes per row, anything else one lane per column.  A plan serves one
+ *                  stream at a time (the chunk sums live in its workspace). */
+int64_t tagrec_rowlist_workspace(int64_t n_listed, int width);
+int64_t tagrec_rowlist_plan_result(int64_t n_listed, int width, int part);
+int tagrec_rowlist_plan_i64(const int64_t* rows, int64_t n_listed, int64_t n, int width, void* ws, int64_t ws_bytes,
+                            void* stream);
+int tagrec_row_scatter_ordered_f32(const void* ws, int64_t ws_bytes, int64_t n_listed, int width, const float* src,
+                                   int64_t lds, float* dst, int64_t ldd, int64_t n_dst, int D, int accumulate, void* stream);
 /* tagrec_spmm_normbwd_dot_f32 (column-sharded tables) on a row-sparse G_in */
 int tagrec_spmm_normbwd_dot_sparse_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
                                        const unsigned* in_count, const float* X_raw, const float* inv_norm,

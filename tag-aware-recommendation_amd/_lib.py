@@ -20,6 +20,12 @@ class TagrecError(RuntimeError):
     pass
 
 
+def refuse_deterministic(config, model, not_covered):
+    """Models without a fixed-order step refuse config["deterministic"] = True loudly instead of ignoring it."""
+    if config.get("deterministic", False):
+        raise TagrecError(f"{model}: deterministic=True is not covered (only the LightGCN and NGCF steps are): {not_covered}")
+
+
 # name -> (argtypes); every function returns int except the two noted below
 _SIGNATURES = {
     "tagrec_abi_version": [],
@@ -151,6 +157,11 @@ _SIGNATURES = {
     "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "tagrec_rowlist_workspace": [c_int64, c_int],
+    "tagrec_rowlist_plan_result": [c_int64, c_int, c_int],
+    "tagrec_rowlist_plan_i64": [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p],
+    "tagrec_row_scatter_ordered_f32": [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                       c_int, c_void_p],
     "tagrec_row_flags_f32": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
     "tagrec_dh_edge_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "tagrec_dh_edge_softmax_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

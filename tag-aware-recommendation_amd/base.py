@@ -4,7 +4,7 @@ row slices are the reference's per-type tables, the `embed.k` state-dict layout,
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, rowops
 from .cor import cor_loss
 
 
@@ -13,9 +13,12 @@ def layer_seed(seed, k):
     return (int(seed) * 64 + k) & 0xFFFFFFFFFFFFFFFF
 
 
-def scatter_rows(n, rows, compact):
-    """[n, D] tensor that holds sum of compact[j] over rows[j] == r at the listed rows and is UNWRITTEN elsewhere."""
+def scatter_rows(n, rows, compact, plan=None):
+    """[n, D] tensor that holds sum of compact[j] over rows[j] == r at the listed rows and is UNWRITTEN elsewhere.
+    plan (`rowops.row_list_plan` of rows): summed in the plan's fixed order, without float atomics."""
     t = torch.empty(n, compact.shape[1], dtype=torch.float32, device=compact.device)
+    if plan is not None:
+        return rowops.scatter_rows_ordered(t, plan, compact, False)
     t.index_fill_(0, rows, 0.0)
     return t.index_add_(0, rows, compact)
 

@@ -18,6 +18,7 @@ _BASE = {
     "node_drop_mode": "rebuild",   # "kernel": edge dropout evaluated inside the products (help.node_drop), no CSR rebuilt per step
     "seed": 2020, "cpu_core": 4, "split_adj_k": 1,
     "hip_graph": False,       # Basic_train: replay each phase's step as one captured HIP graph (train.GraphedStep)
+    "deterministic": False,   # LightGCN / NGCF: fold batch gradients in a fixed order (rowops.scatter_rows_ordered), no float atomics
     "all_gather": "collective",   # row-sharded models (dist.py): "direct" = one grouped send / receive pair per peer
 }
 

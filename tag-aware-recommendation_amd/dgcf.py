@@ -15,7 +15,7 @@ weights carry no gradient in the reference (`A_factor.detach()`, :93), so backwa
 normalise-backward followed by one routed product with the transposed weights of the LAST iteration."""
 import torch
 
-from . import help as H
+from . import _lib, help as H
 from . import routing as R
 from .base import TableModel
 from .config import CFG as _GLOBAL_CFG
@@ -68,6 +68,7 @@ class DGCF(TableModel):
         self.routing = R.RoutingGraph(self.norm_adj)
 
     def _config(self, config):
+        _lib.refuse_deterministic(config, "DGCF", "the backward of its torch gathers sums repeated batch rows with float atomics")
         self.dim_latent = config["dim_latent"]
         self.num_layer = len(config["dim_layer_list"])
         self.device = torch.device(config["device"])

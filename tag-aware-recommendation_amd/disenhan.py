@@ -242,6 +242,7 @@ class DisenHAN(TableModel):
         self.layer.to(self.device)
 
     def _config(self, config):
+        _lib.refuse_deterministic(config, "DisenHAN", "the backward of its torch gathers sums repeated batch rows with float atomics")
         self.dim_latent = config["dim_latent"]
         self.num_layer = len(config["dim_layer_list"])
         self.device = torch.device(config["device"])

@@ -529,6 +529,7 @@ class ShardedLightGCN(torch.nn.Module):
 
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None, n_chunks=None, symmetric=None):
         super().__init__()
+        _lib.refuse_deterministic(config, "ShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -922,6 +923,7 @@ class ShardedNGCF(torch.nn.Module):
 
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None, n_chunks=None):
         super().__init__()
+        _lib.refuse_deterministic(config, "ShardedNGCF", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -1204,6 +1206,7 @@ class FeatureShardedLightGCN(torch.nn.Module):
 
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None):
         super().__init__()
+        _lib.refuse_deterministic(config, "FeatureShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)

@@ -43,6 +43,7 @@ class KGAT(nn.Module):
         self._eval_cache = None
 
     def _config(self, config):
+        _lib.refuse_deterministic(config, "KGAT", "the backward of its torch gathers sums repeated batch rows with float atomics")
         self.dim_latent = config["dim_latent"]
         self.dim_relation = config["dim_relation"]
         self.dim_layer_list = list(config["dim_layer_list"])

@@ -173,11 +173,20 @@ def batch_hop_plan(graph_t, rows, ws=None):
     return src.batch_hop_plan(rows, cap, buf)
 
 
-def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=None):
+def row_plan(rows, n, D, ws=None):
+    """The step's `rowops.row_list_plan` of the batch rows (deterministic mode): one plan, kept in the step workspace, serves
+    every fold of the step's compact [3 B, D] gradients into [n, D] tables."""
+    buf = step_buffer(ws, "row_plan", (rowops.row_list_workspace(rows.numel(), D),), torch.uint8, rows.device)
+    return rowops.row_list_plan(rows, n, buf, D)
+
+
+def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=None, plan=None):
     """Gradient w.r.t. x0 of `restricted_forward` given d_out_b [T, D] = d loss / d out_b.  The chain starts on the batch
     rows (compact), lands on their neighbours (row-masked hop: G is non-zero there only) and spreads from there; every
     operand travels with one flag byte per row and zero rows are not gathered; the normalize-backward / mean terms exist
-    on the batch rows only (dz_flags), so no other row's epilogue reads X_raw or dZ."""
+    on the batch rows only (dz_flags), so no other row's epilogue reads X_raw or dZ.
+    plan (`row_plan` of rows): the compact gradients are folded onto the batch rows in a fixed order instead of by
+    `index_add_` (float atomics where a batch names a node twice)."""
     raws, invs, mid, y_top, inv_top = state
     n, D = shape
     L = len(raws) + 1
@@ -187,15 +196,21 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
     tflag = step_buffer(ws, "tflag", (n,), torch.uint8, dev).zero_()
     tflag.index_fill_(0, rows, 1)
     dz = step_buffer(ws, "dz", (n, D), torch.float32, dev)              # d loss / d out, valid on the batch rows only
-    dz.index_fill_(0, rows, 0.0)
-    dz.index_add_(0, rows, d_out_b)
+    if plan is not None:
+        rowops.scatter_rows_ordered(dz, plan, d_out_b, False)
+    else:
+        dz.index_fill_(0, rows, 0.0)
+        dz.index_add_(0, rows, d_out_b)
     g_top = torch.empty(T, D, dtype=torch.float32, device=dev)
     rowops.rownorm_bwd(y_top, inv_top, d_out_b, s, g_top)
     g = step_buffer(ws, "g_top", (n, D), torch.float32, dev)             # G^L: valid on the batch rows only (flags = tflag)
-    g.index_fill_(0, rows, 0.0)
-    g.index_add_(0, rows, g_top)
+    if plan is not None:
+        rowops.scatter_rows_ordered(g, plan, g_top, False)
+    else:
+        g.index_fill_(0, rows, 0.0)
+        g.index_add_(0, rows, g_top)
     flags, count = tflag, None                                           # count None: the flags are always consulted
-    plan = batch_hop_plan(graph_t, rows, ws) if L >= 2 else None
+    hop = batch_hop_plan(graph_t, rows, ws) if L >= 2 else None
     for k in range(L - 2, -1, -1):
         masked = k == L - 2
         gn = step_buffer(ws, f"g{k & 1}", (n, D), torch.float32, dev)
@@ -203,8 +218,8 @@ def restricted_backward(graph_t, rows, d_out_b, state, shape, fused=None, ws=Non
         if masked:
             fo.zero_()
         cnt = step_buffer(ws, f"cnt{k & 1}", (1,), torch.int32, dev).zero_()
-        if masked and plan is not None:   # rows of `mid` without a record or a dz term stay unwritten, their flag zero
-            graph_t.batch_hop_normbwd(plan, g, raws[k], invs[k], dz, s, gn, fo, mid, tflag)
+        if masked and hop is not None:    # rows of `mid` without a record or a dz term stay unwritten, their flag zero
+            graph_t.batch_hop_normbwd(hop, g, raws[k], invs[k], dz, s, gn, fo, mid, tflag)
         else:
             graph_t.spmm_normbwd_sparse(g, flags, count, raws[k], invs[k], dz, s, gn, fo, cnt, row_mask=mid if masked else None,
                                         dz_flags=tflag)
@@ -240,7 +255,7 @@ class _PropagateBprLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active, drops=None, seed=0, restrict=True,
-                fused_opt=None, ws=None):
+                fused_opt=None, ws=None, deterministic=False):
         x0 = table.detach()
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         ctx.ws, ctx.token = None, _Token()
@@ -250,7 +265,9 @@ class _PropagateBprLoss(torch.autograd.Function):
         n = x0.shape[0]
         ctx.n_user, ctx.n_item, ctx.reg_active, ctx.trip, ctx.graph = n_user, n_item, reg_active, trip, graph
         # the loss reads `out` at the batch rows only: users, and items offset by n_user
-        rows = rowops.batch_rows(trip, n_user) if restrict else None
+        rows = rowops.batch_rows(trip, n_user) if (restrict or deterministic) else None
+        # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
+        ctx.plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
         ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
                            and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
         if ctx.compact:
@@ -261,7 +278,7 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.rows, ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.shape = rows, out_b, ego_b, ctrip, x0.shape
             return res
         ctx.masks = {}
-        out, raws, invs = propagate_forward(graph, x0, n_layer, drops, seed, rows, ctx.masks)
+        out, raws, invs = propagate_forward(graph, x0, n_layer, drops, seed, rows if restrict else None, ctx.masks)
         ctx.drops, ctx.seed = drops, seed
         U, I = out[:n_user], out[n_user:n_user + n_item]
         Ue, Ie = x0[:n_user], x0[n_user:n_user + n_item]
@@ -279,28 +296,35 @@ class _PropagateBprLoss(torch.autograd.Function):
             Ue, Ie, dUe, dIe = (ego_b[:B], ego_b[B:], d_b[1][:B], d_b[1][B:]) if ctx.reg_active else (None,) * 4
             rowops.bpr_bwd(out_b[:B], out_b[B:], Ue, Ie, ctrip, ctx.coef, g, d_b[0][:B], d_b[0][B:], dUe, dIe)
             fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
-            g0 = restricted_backward(ctx.graph.transpose(), rows, d_b[0], ctx.state, ctx.shape, fused, ctx.ws)
-            if ctx.reg_active:
+            g0 = restricted_backward(ctx.graph.transpose(), rows, d_b[0], ctx.state, ctx.shape, fused, ctx.ws, ctx.plan)
+            if ctx.reg_active and ctx.plan is not None:
+                rowops.scatter_rows_ordered(g0, ctx.plan, d_b[1], True)   # L2 term on the ego rows
+            elif ctx.reg_active:
                 g0.index_add_(0, rows, d_b[1])                            # L2 term on the ego rows
             ctx.state = ctx.out_b = None
             if ctx.ws is not None:
                 ctx.ws.release(ctx.token)
-            return g0, None, None, None, None, None, None, None, None, None, None, None, None
+            return g0, None, None, None, None, None, None, None, None, None, None, None, None, None
         out, x0, trip = ctx.out, ctx.x0, ctx.trip
         nu, ni = ctx.n_user, ctx.n_item
         d_out = torch.zeros_like(out)
         U, I = out[:nu], out[nu:nu + ni]
-        rowops.bpr_bwd(U, I, None, None, trip, ctx.coef, g, d_out[:nu], d_out[nu:nu + ni], None, None)
+        if ctx.plan is not None:
+            rowops.bpr_bwd_ordered(out, None, trip, ctx.coef, g, d_out, None, ctx.plan)
+        else:
+            rowops.bpr_bwd(U, I, None, None, trip, ctx.coef, g, d_out[:nu], d_out[nu:nu + ni], None, None)
         fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active and len(ctx.raws) >= 1) else None
         g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
         # L2 term on the ego rows: added after the propagation hop has written g0
-        if ctx.reg_active:
+        if ctx.reg_active and ctx.plan is not None:
+            rowops.bpr_bwd_ordered(out, x0, trip, ctx.coef, g, None, g0, ctx.plan, True, "bpr_bwd(reg)")
+        elif ctx.reg_active:
             Ue, Ie = x0[:nu], x0[nu:nu + ni]
             rowops.bpr_bwd(U, I, Ue, Ie, trip, ctx.coef, g, None, None, g0[:nu], g0[nu:nu + ni], "bpr_bwd(reg)")
         ctx.raws = ctx.invs = ctx.out = None
         if ctx.ws is not None:
             ctx.ws.release(ctx.token)
-        return g0, None, None, None, None, None, None, None, None, None, None, None, None
+        return g0, None, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class LightGCN(FusedStepModel):
@@ -331,6 +355,8 @@ class LightGCN(FusedStepModel):
         self.restrict_forward = bool(config.get("restrict_forward", True))
         # persistent buffers of the restricted training step (base.StepWorkspace); config["step_workspace"] = False: allocate per step
         self.step_ws = StepWorkspace() if config.get("step_workspace", True) else None
+        # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
+        self.deterministic = bool(config.get("deterministic", False))
 
     def _fused_ok(self):
         return isinstance(self.norm_adj, Graph)
@@ -385,8 +411,11 @@ class LightGCN(FusedStepModel):
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
             res = _PropagateBprLoss.apply(self.table, graph, self.num_layer, nu, ni, batch_data,
                                           H.loss_kind_id(self.loss_func), self.reg != 0, drops, seed, self.restrict_forward,
-                                          fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None)
+                                          fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None,
+                                          self.deterministic)
             return res[0], self.reg * res[1]
+        if self.deterministic:
+            raise _lib.TagrecError("LightGCN: deterministic=True covers the fused step only (no row folds: split_adj_k == 1)")
         all_users, all_items = self.forward()[:2]
         ego = self.embed
         loss, reg_loss = H.triplet_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func)

@@ -83,12 +83,14 @@ def _dxp_through_dropout(dx_next, xp, inv, dz, p, seed, rows=None):
     return H.message_drop(g, p, seed, out=g, rows=rows)
 
 
-def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
+def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0, deterministic=False):
     """x0 [N, dims[0]] -> out [N, sum(dims)] = cat(x0, z1..zL) and the per-layer state for backward.
 
     loss_rows (int64 node ids): `out` will be read at these rows only (the batch rows).  Then the last layer's
     neighbour sum is formed for them alone and the one below it for their neighbours (marked through the adjacency
-    rows; further down every row is needed); the other rows of those layers carry values that nothing reads."""
+    rows; further down every row is needed); the other rows of those layers carry values that nothing reads.
+    deterministic: the backward pass folds the top layer's compact gradients in a fixed order (the `rowops.row_list_plan` of
+    the sorted batch rows is built here) instead of by `index_add_`."""
     n = x0.shape[0]
     dtot = sum(dims)
     out = torch.empty(n, dtot, dtype=torch.float32, device=x0.device)
@@ -112,6 +114,7 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
             rows, _ = torch.sort(loss_rows)
             first = torch.ones_like(rows, dtype=torch.bool)
             first[1:] = rows[1:] != rows[:-1]
+            tplan = rowops.row_list_plan(rows, n, None, max(dims)) if deterministic else None   # fixed-order folds in the backward pass
             xc, nc = x.index_select(0, rows), nei.index_select(0, rows)
             d = dims[k + 1]
             xpc = torch.empty(rows.numel(), d, dtype=torch.float32, device=x0.device)
@@ -122,7 +125,7 @@ def propagate_forward(graph, x0, wps, dims, loss_rows=None, drops=None, seed=0):
             if pk > 0:                      # the node's mask (keyed by node id): every slot of a repeated node is identical
                 _drop_renorm(xpc, invc, zc, pk, _layer_seed(seed, k), rows)
             out[:, off:off + d].index_copy_(0, rows, zc)          # the other rows of this slot are never read
-            saved.append(("rows", (rows, first), masks[k], masks.get(k - 1), xc, nc, xpc, invc, w1p, w2p, pk, _layer_seed(seed, k)))
+            saved.append(("rows", (rows, first, tplan), masks[k], masks.get(k - 1), xc, nc, xpc, invc, w1p, w2p, pk, _layer_seed(seed, k)))
             break
         xp = torch.empty(n, dims[k + 1], dtype=torch.float32, device=x0.device)
         inv = torch.empty(n, dtype=torch.float32, device=x0.device)
@@ -145,7 +148,7 @@ def propagate_backward(graph_t, d_out, saved, dims):
     dx_next = None
     for k in range(len(saved) - 1, -1, -1):
         if isinstance(saved[k][0], str):                       # the top layer of a restricted forward pass: batch rows only
-            _, (rows, first), mask, reach, xc, nc, xpc, invc, w1p, w2p, pk, sk = saved[k]
+            _, (rows, first, tplan), mask, reach, xc, nc, xpc, invc, w1p, w2p, pk, sk = saved[k]
             d = dims[k + 1]
             dzc = d_out[:, offs[k + 1]:offs[k + 1] + d].index_select(0, rows) * first[:, None]     # one slot per node
             if pk > 0:
@@ -154,8 +157,14 @@ def propagate_backward(graph_t, d_out, saved, dims):
                 d_nei_c, d_xd_c, dw1, dw2 = dense_backward(None, nc, xc, w1p, w2p, norm=(xpc, invc, dzc, d))
             dws[k] = (dw1, dw2)
             din = xc.shape[1]
-            d_nei = torch.zeros(n, din, dtype=torch.float32, device=xc.device).index_add_(0, rows, d_nei_c)
-            d_xd = torch.zeros(n, din, dtype=torch.float32, device=xc.device).index_add_(0, rows, d_xd_c)
+            d_nei = torch.zeros(n, din, dtype=torch.float32, device=xc.device)
+            d_xd = torch.zeros(n, din, dtype=torch.float32, device=xc.device)
+            if tplan is not None:
+                rowops.scatter_rows_ordered(d_nei, tplan, d_nei_c, False)
+                rowops.scatter_rows_ordered(d_xd, tplan, d_xd_c, False)
+            else:
+                d_nei.index_add_(0, rows, d_nei_c)
+                d_xd.index_add_(0, rows, d_xd_c)
             count = torch.full((1,), rows.numel(), dtype=torch.int32, device=xc.device)
             # d_nei and d_xd live on the batch rows, so dx is zero outside `reach` = those rows and their neighbours (the
             # mask the layer below was computed on): only they are visited
@@ -236,11 +245,13 @@ def restricted_forward(graph, x0, wps, dims, rows):
     return out_b, (saved, mid, (nc, xc, xpc, invc, w1p, w2p))
 
 
-def restricted_backward(graph_t, rows, d_b, state, dims, n, fused=None):
+def restricted_backward(graph_t, rows, d_b, state, dims, n, fused=None, plan=None):
     """Gradient of `restricted_forward` given d_b [T, sum(dims)] = d loss / d out_b -> (d_x0 [n, dims[0]], [(dW1', dW2')]).
     The chain starts on the batch rows (compact), lands on their neighbours (row-masked hop) and spreads from there; the
     concat gradient of the lower layers lives on the batch rows (dz_flags), the masked layer's dense backward and weight
-    gradient visit the masked rows only, and every product is told which operand rows are valid."""
+    gradient visit the masked rows only, and every product is told which operand rows are valid.
+    plan (`rowops.row_list_plan` of rows): the compact gradients are folded onto the batch rows in a fixed order instead of
+    by `index_add_` (float atomics where a batch names a node twice)."""
     saved, mid, (nc, xc, xpc, invc, w1p, w2p) = state
     L = len(saved) + 1
     dtot = d_b.shape[1]
@@ -254,12 +265,15 @@ def restricted_backward(graph_t, rows, d_b, state, dims, n, fused=None):
     # top layer, one slot per batch row
     d_nei_c, d_xd_c, dw1, dw2 = dense_backward(None, nc, xc, w1p, w2p, norm=(xpc, invc, d_b[:, offs[L]:], dtot))
     dws[L - 1] = (dw1, dw2)
-    g, b = _scatter_rows(n, rows, d_nei_c), _scatter_rows(n, rows, d_xd_c)       # valid on the batch rows only
+    g, b = _scatter_rows(n, rows, d_nei_c, plan), _scatter_rows(n, rows, d_xd_c, plan)       # valid on the batch rows only
 
     def last_product(g_in, in_flags, addend, b_flags):
         """The product that lands on the table: d x0 = A^T g_in + addend (+ the concat gradient's first slot, which lives on
         the batch rows and is folded into the addend first) -- or, with a fused optimizer, Adam applied in its epilogue."""
-        addend.index_add_(0, rows, d_b[:, :dims[0]])
+        if plan is not None:
+            rowops.scatter_rows_ordered(addend, plan, d_b[:, :dims[0]], True)
+        else:
+            addend.index_add_(0, rows, d_b[:, :dims[0]])
         if fused is not None:
             fused_last_hop(graph_t, fused, g_in, in_flags, None, addend, 1.0, b_flags)
             return None
@@ -275,7 +289,7 @@ def restricted_backward(graph_t, rows, d_b, state, dims, n, fused=None):
     dx = torch.empty(n, dims[L - 1], dtype=torch.float32, device=dev)
     graph_t.spmm_axpy_sparse(g, tflag, None, b, 1.0, dx, mid, b_flags=tflag)     # valid on `mid`
     if L >= 2:
-        dzn = _scatter_rows(n, rows, d_b[:, offs[1]:offs[L]])                    # concat gradient of layers 1 .. L-1
+        dzn = _scatter_rows(n, rows, d_b[:, offs[1]:offs[L]], plan)                  # concat gradient of layers 1 .. L-1
         ldz = dzn.shape[1]
     for k in range(L - 2, -1, -1):
         x, nei, xp, inv, w1p, w2p, m = saved[k]
@@ -322,12 +336,14 @@ class _PropagateBprLoss(torch.autograd.Function):
     """(table, mats) -> [mul_loss, l2reg_loss(propagated rows)] in one autograd node."""
 
     @staticmethod
-    def forward(ctx, graph, dims, n_user, n_item, trip, loss_kind, drops, seed, fused_opt, table, *mats):
+    def forward(ctx, graph, dims, n_user, n_item, trip, loss_kind, drops, seed, fused_opt, deterministic, table, *mats):
         x0 = table.detach()
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         wps = _wps([m.detach() for m in mats])
         B, n = trip.shape[0], x0.shape[0]
-        rows = rowops.batch_rows(trip, n_user) if RESTRICT_FORWARD else None
+        rows = rowops.batch_rows(trip, n_user) if (RESTRICT_FORWARD or deterministic) else None
+        # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
+        ctx.plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
         ctx.graph, ctx.dims, ctx.trip, ctx.nu, ctx.ni = graph, dims, trip, n_user, n_item
         ctx.compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
                            and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
@@ -338,7 +354,7 @@ class _PropagateBprLoss(torch.autograd.Function):
             res, ctx.coef = rowops.bpr_fwd(U, I, U, I, ctrip, loss_kind)
             ctx.rows, ctx.out_b, ctx.ctrip, ctx.n = rows, out_b, ctrip, n
             return res
-        out, saved = propagate_forward(graph, x0, wps, dims, rows, drops, seed)
+        out, saved = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
         U, I = out[:n_user], out[n_user:n_user + n_item]
         res, ctx.coef = rowops.bpr_fwd(U, I, U, I, trip, loss_kind)
         ctx.saved, ctx.out = saved, out
@@ -352,17 +368,20 @@ class _PropagateBprLoss(torch.autograd.Function):
             d_b = torch.zeros_like(out_b)
             U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
             rowops.bpr_bwd(U, I, U, I, ctrip, ctx.coef, g, dU, dI, dU, dI)
-            d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused)
+            d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
             ctx.state = ctx.out_b = None
-            return (None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
+            return (None, None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
         out, trip, nu, ni = ctx.out, ctx.trip, ctx.nu, ctx.ni
         d_out = torch.zeros_like(out)
         U, I = out[:nu], out[nu:nu + ni]
         dU, dI = d_out[:nu], d_out[nu:nu + ni]
-        rowops.bpr_bwd(U, I, U, I, trip, ctx.coef, g, dU, dI, dU, dI)
+        if ctx.plan is not None:
+            rowops.bpr_bwd_ordered(out, out, trip, ctx.coef, g, d_out, d_out, ctx.plan)
+        else:
+            rowops.bpr_bwd(U, I, U, I, trip, ctx.coef, g, dU, dI, dU, dI)
         d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
         ctx.saved = ctx.out = None
-        return (None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
+        return (None, None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
 
 
 class NGCF(FusedStepModel):
@@ -395,6 +414,8 @@ class NGCF(FusedStepModel):
         self.loss_func = config["mul_loss_func"]
         self.use_tag = config["use_tag"]
         self.drop_seed = config.get("seed", 2020)
+        # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
+        self.deterministic = bool(config.get("deterministic", False))
 
     def _mats(self):
         return [self.mat[f"{n}_{k}"] for k in range(self.num_layer) for n in ("W1", "b1", "W2", "b2")]
@@ -433,8 +454,12 @@ class NGCF(FusedStepModel):
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
             res = _PropagateBprLoss.apply(self.norm_adj, tuple(self.dim_layer_list), nu, ni, batch_data,
-                                          H.loss_kind_id(self.loss_func), drops, seed, fused, self.table, *self._mats())
+                                          H.loss_kind_id(self.loss_func), drops, seed, fused, self.deterministic, self.table,
+                                          *self._mats())
             return res[0], self.reg * res[1]
+        if self.deterministic:
+            raise _lib.TagrecError("NGCF: deterministic=True covers the fused step only (bi_agg, widths in {16, 32, 64, 128}, "
+                                   "no row folds)")
         all_users, all_items = self.forward()[:2]
         loss, reg_loss = H.triplet_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func)
         return loss, self.reg * reg_loss

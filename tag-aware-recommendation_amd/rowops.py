@@ -126,3 +126,95 @@ def compact_triplets(B, device):
 def batch_rows(trip, n_user):
     """Node ids [3 B] of a triplet batch in the [user | item] table: users, then positive and negative items."""
     return torch.cat([trip[:, 0], n_user + trip[:, 1], n_user + trip[:, 2]])
+
+
+# ---- fixed-order scatter of compact rows (csrc/rowscatter.hip): the `deterministic` mode of LightGCN / NGCF ----
+
+class RowListPlan:
+    """A row list (int64 node ids [T], may repeat) sorted into segments, one per distinct id, built on the device without a
+    host read.  `order` (int32 [T]): the slots stably sorted by row id; `seg_row` / `seg_ptr` (int32 [T] / [T + 1]): the
+    distinct rows ascending and where their slots start in `order`, valid up to the device-side segment count; `counts`
+    (int32 [4]): segments, valid slots, ids outside [0, n).  All are views of `workspace`, which also holds the scatter's
+    chunk sums: a plan serves one stream at a time and lives until its workspace is planned again."""
+    __slots__ = ("rows", "n", "width", "workspace", "order", "seg_row", "seg_ptr", "counts")
+
+    def segments(self):
+        """(seg_row [S], seg_ptr [S + 1]) -- reads the segment count back to the host."""
+        S = int(self.counts[0])
+        return self.seg_row[:S], self.seg_ptr[:S + 1]
+
+    def dropped(self):
+        """Number of ids outside [0, n) that the plan left out -- reads the device counter back to the host."""
+        return int(self.counts[2])
+
+
+def row_list_workspace(n_listed, width):
+    """Bytes of the workspace of a plan over n_listed rows whose scatters are at most `width` floats wide."""
+    nbytes = load().tagrec_rowlist_workspace(n_listed, width)
+    if nbytes <= 0:
+        check(-1, "rowlist_workspace")
+    return nbytes
+
+
+def row_list_plan(rows, n, workspace=None, width=256):
+    """-> RowListPlan of `rows` (int64 [T] ids into a table of n rows).  workspace: uint8 tensor of at least
+    `row_list_workspace(T, width)` bytes (None: allocated here); width: the widest row the plan will scatter."""
+    rows = _lib.require_gpu_tensor(rows, torch.int64, "row_list_plan: rows")
+    T = rows.numel()
+    need = row_list_workspace(T, width)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != rows.device or not workspace.is_contiguous():
+        raise _lib.TagrecError(f"row_list_plan: the workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
+    lib = load()
+    check(lib.tagrec_rowlist_plan_i64(ptr(rows), T, n, width, ptr(workspace), workspace.numel(), stream_ptr()), "rowlist_plan")
+    p = RowListPlan()
+    p.rows, p.n, p.width, p.workspace = rows, n, width, workspace
+    at = [lib.tagrec_rowlist_plan_result(T, width, k) for k in range(4)]
+    p.order = workspace[at[0]:at[0] + 4 * T].view(torch.int32)
+    p.seg_row = workspace[at[1]:at[1] + 4 * T].view(torch.int32)
+    p.seg_ptr = workspace[at[2]:at[2] + 4 * (T + 1)].view(torch.int32)
+    p.counts = workspace[at[3]:at[3] + 16].view(torch.int32)
+    return p
+
+
+def scatter_rows_ordered(dst, plan, src, accumulate):
+    """dst[r] (=|+=) sum of src[j] over plan.rows[j] == r, in ascending j (chunks of 1024: see include/tagrec.h); rows of dst
+    the list does not name are not touched.  No float atomics: the same bits on every run.  src [T, D], dst [>= plan.n, D];
+    both may have a row stride larger than D."""
+    T = plan.rows.numel()
+    if src.dim() != 2 or dst.dim() != 2 or src.shape[0] != T or src.shape[1] != dst.shape[1] or dst.shape[0] < plan.n:
+        raise _lib.TagrecError(f"scatter_rows_ordered: src {tuple(src.shape)} must be [{T}, D] and dst {tuple(dst.shape)} "
+                               f"[>= {plan.n}, D]")
+    for nm, t in (("src", src), ("dst", dst)):
+        if not t.is_cuda or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise _lib.TagrecError(f"scatter_rows_ordered: {nm} must be a float32 GPU tensor with unit inner stride")
+    D = src.shape[1]
+    check(load().tagrec_row_scatter_ordered_f32(ptr(plan.workspace), plan.workspace.numel(), T, plan.width, ptr(src),
+                                                src.stride(0) if T > 1 else D, ptr(dst), dst.stride(0) if dst.shape[0] > 1 else D,
+                                                dst.shape[0], D, int(bool(accumulate)), stream_ptr()), "row_scatter_ordered")
+    return dst
+
+
+def bpr_bwd_ordered(out, ego, trip, coef, g, d_out, d_ego, plan, accumulate=False, what="bpr_bwd_ordered"):
+    """`bpr_bwd` for triplets that index the real [user | item] tables, without float atomics on repeated rows: the 3 B operand
+    rows are gathered, `bpr_bwd` runs on `compact_triplets` (every slot its own row: nothing collides) and the compact
+    gradients are folded with `scatter_rows_ordered`.  out / ego: the tables of the main and the L2 part (ego None: no L2
+    part); d_out / d_ego: where their gradients land (d_out None: the L2 part only; d_ego may be d_out); plan: the
+    `row_list_plan` of `batch_rows(trip, n_user)`."""
+    B = trip.shape[0]
+    rows = plan.rows
+    ctrip = compact_triplets(B, out.device)
+    out_b = out.index_select(0, rows)
+    d_b = None if d_out is None else torch.zeros_like(out_b)
+    dU, dI = (None, None) if d_b is None else (d_b[:B], d_b[B:])
+    Ue = Ie = dUe = dIe = d_e = None
+    if ego is not None:
+        ego_b = out_b if ego is out else ego.index_select(0, rows)
+        d_e = d_b if (d_ego is d_out and d_b is not None) else torch.zeros_like(ego_b)
+        Ue, Ie, dUe, dIe = ego_b[:B], ego_b[B:], d_e[:B], d_e[B:]
+    bpr_bwd(out_b[:B], out_b[B:], Ue, Ie, ctrip, coef, g, dU, dI, dUe, dIe, what)
+    if d_b is not None:
+        scatter_rows_ordered(d_out, plan, d_b, accumulate)
+    if d_e is not None and d_e is not d_b:
+        scatter_rows_ordered(d_ego, plan, d_e, accumulate)

@@ -321,11 +321,48 @@ class Graph:
             raise _lib.TagrecError(f"{name}: expected [{rows}, D], got {tuple(X.shape)}")
         return int(X.shape[1])
 
+    def _chk_w(self, t, rows, D, name):
+        """[rows, D] float32 on this graph's device (an output or epilogue operand of a product of width D)."""
+        if self._chk_x(t, rows, name) != D:
+            raise _lib.TagrecError(f"{name}: width {t.shape[1]} where the gathered operand has {D}")
+        self._chk_dev(t, name)
+
+    def _chk_dev(self, t, name):
+        if t.device != self.device:
+            raise _lib.TagrecError(f"{name}: on {t.device}, the graph is on {self.device}")
+
+    def _chk_vec(self, t, n, dtype, name, optional=False):
+        """One `dtype` element per row / column: a 1-D tensor of exactly n elements (row flags, masks, inverse norms)."""
+        if t is None and optional:
+            return
+        _lib.require_gpu_tensor(t, dtype, name)
+        if t.dim() != 1 or t.numel() != n:
+            raise _lib.TagrecError(f"{name}: expected [{n}], got {tuple(t.shape)}")
+        self._chk_dev(t, name)
+
+    def _chk_count(self, t, name):
+        """Optional device counter of flagged rows: int32, at least one element."""
+        if t is None:
+            return
+        _lib.require_gpu_tensor(t, torch.int32, name)
+        if t.numel() < 1:
+            raise _lib.TagrecError(f"{name}: empty counter")
+        self._chk_dev(t, name)
+
+    def _chk_rows(self, rows, name):
+        rows = rows.contiguous() if isinstance(rows, torch.Tensor) else rows
+        _lib.require_gpu_tensor(rows, torch.int64, name)
+        if rows.dim() != 1:
+            raise _lib.TagrecError(f"{name}: expected a 1-D list of row ids, got {tuple(rows.shape)}")
+        self._chk_dev(rows, name)
+        return rows
+
     def spmm(self, X, out=None):
         D = self._chk_x(X, self.shape[1], "spmm X")
         if out is None:
             out = torch.empty(self.shape[0], D, dtype=torch.float32, device=X.device)
-        self._chk_x(out, self.shape[0], "spmm out")
+        self._chk_w(out, self.shape[0], D, "spmm out")
+        self._chk_dev(X, "spmm X")
         self._call("spmm", _lib.load().tagrec_spmm_f32, self._h, _lib.ptr(X), _lib.ptr(out), D, _lib.stream_ptr())
         return out
 
@@ -346,24 +383,34 @@ class Graph:
 
     def mark_rows(self, rows, flags):
         """flags[c] = 1 for every column stored in `rows` (int64 node ids) and for the rows themselves."""
-        rows = rows.contiguous()
+        rows = self._chk_rows(rows, "mark_rows rows")
+        if self.shape[0] != self.shape[1]:
+            raise _lib.TagrecError("mark_rows: square adjacency expected (flags are indexed by node)")
+        self._chk_vec(flags, self.shape[0], torch.uint8, "mark_rows flags")
         _lib.check(_lib.load().tagrec_graph_mark_rows_u8(self._h, _lib.ptr(rows), rows.numel(), _lib.ptr(flags),
                                                          _lib.stream_ptr()), "graph_mark_rows")
         return flags
 
     def spmm_rows(self, X, out, row_mask):
         """`spmm` for the rows with row_mask[r] != 0 (the others of `out` are left as they are)."""
-        D = self._chk_x(X, self.shape[1], "spmm X")
+        D = self._chk_x(X, self.shape[1], "spmm_rows X")
+        self._chk_w(out, self.shape[0], D, "spmm_rows out")
+        self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_rows row_mask")
         self._call("spmm_rows", _lib.load().tagrec_spmm_rows_f32, self._h, _lib.ptr(X), _lib.ptr(out), _lib.ptr(row_mask), D,
                    _lib.stream_ptr())
         return out
 
     def spmm_listed(self, rows, X, out=None):
         """(A X)[rows] as a compact [len(rows), D] tensor (rows int64, may repeat)."""
-        rows = rows.contiguous()
+        rows = self._chk_rows(rows, "spmm_listed rows")
         lib = _lib.load()
+        D = self._chk_x(X, self.shape[1], "spmm_listed X")
+        self._chk_dev(X, "spmm_listed X")
         if out is None:
-            out = torch.empty(rows.numel(), X.shape[1], dtype=torch.float32, device=X.device)
+            out = torch.empty(rows.numel(), D, dtype=torch.float32, device=X.device)
+        self._chk_w(out, rows.numel(), D, "spmm_listed out")
+        if rows.numel() == 0:             # nothing listed: the empty result (an empty tensor has no address to hand over)
+            return out
         ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), X.shape[1])
         ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
         self._call("spmm_listed", lib.tagrec_spmm_listed_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
@@ -373,11 +420,38 @@ class Graph:
     def spmm_norm_acc_rows(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, drop_p=0.0, seed=0):
         """`spmm_norm_acc` for the rows with row_mask[r] != 0 only (the others are left as they are; None = every row).
         acc None: the layer mean is not accumulated."""
-        D = self._chk_x(X, self.shape[1], "spmm_norm_acc X")
+        D = self._chk_x(X, self.shape[1], "spmm_norm_acc_rows X")
+        self._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
         self._call("spmm_norm_acc_rows" if row_mask is not None else "spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_rows_f32,
                    self._h, _lib.ptr(X), _lib.ptr(y_raw),
                    _lib.ptr(inv_norm), _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), D,
                    _lib.stream_ptr())
+
+    def _chk_norm_acc_rows(self, D, y_raw, inv_norm, acc, row_mask):
+        self._chk_w(y_raw, self.shape[0], D, "spmm_norm_acc_rows y_raw")
+        self._chk_vec(inv_norm, self.shape[0], torch.float32, "spmm_norm_acc_rows inv_norm")
+        if acc is not None:
+            self._chk_w(acc, self.shape[0], D, "spmm_norm_acc_rows acc")
+        self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_norm_acc_rows row_mask", optional=True)
+
+    def _chk_normbwd_sparse(self, D, in_flags, in_count, x_raw, inv_norm, dz, g_out, out_flags, out_count, row_mask, dz_flags):
+        for t, nm in ((x_raw, "x_raw"), (dz, "dz"), (g_out, "g_out")):
+            self._chk_w(t, self.shape[0], D, "spmm_normbwd_sparse " + nm)
+        self._chk_vec(inv_norm, self.shape[0], torch.float32, "spmm_normbwd_sparse inv_norm")
+        self._chk_vec(in_flags, self.shape[1], torch.uint8, "spmm_normbwd_sparse in_flags", optional=True)
+        self._chk_count(in_count, "spmm_normbwd_sparse in_count")
+        self._chk_vec(out_flags, self.shape[0], torch.uint8, "spmm_normbwd_sparse out_flags", optional=True)
+        self._chk_count(out_count, "spmm_normbwd_sparse out_count")
+        self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_normbwd_sparse row_mask", optional=True)
+        self._chk_vec(dz_flags, self.shape[0], torch.uint8, "spmm_normbwd_sparse dz_flags", optional=True)
+
+    def _chk_axpy_sparse(self, D, in_flags, in_count, b, g_out, row_mask, b_flags):
+        for t, nm in ((b, "b"), (g_out, "g_out")):
+            self._chk_w(t, self.shape[0], D, "spmm_axpy_sparse " + nm)
+        self._chk_vec(in_flags, self.shape[1], torch.uint8, "spmm_axpy_sparse in_flags", optional=True)
+        self._chk_count(in_count, "spmm_axpy_sparse in_count")
+        self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_axpy_sparse row_mask", optional=True)
+        self._chk_vec(b_flags, self.shape[0], torch.uint8, "spmm_axpy_sparse b_flags", optional=True)
 
     def spmm_normbwd(self, g_in, x_raw, inv_norm, dz, d_scale, g_out, drop_p=0.0, seed=0):
         D = self._chk_x(g_in, self.shape[1], "spmm_normbwd g_in")
@@ -397,11 +471,8 @@ class Graph:
         """`spmm_normbwd` on a row-sparse g_in: rows whose in_flags byte is 0 are not gathered (same result); writes the
         flags / count of its own output when out_flags is given.  row_mask: rows whose byte is 0 are not touched at all
         (the caller knows their result is zero and has zeroed g_out / out_flags there)."""
-        D = self._chk_x(g_in, self.shape[1], "spmm_normbwd g_in")
-        if row_mask is not None:
-            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
-            if row_mask.numel() != self.shape[0]:
-                raise _lib.TagrecError("spmm_normbwd_sparse: row_mask must have one byte per row")
+        D = self._chk_x(g_in, self.shape[1], "spmm_normbwd_sparse g_in")
+        self._chk_normbwd_sparse(D, in_flags, in_count, x_raw, inv_norm, dz, g_out, out_flags, out_count, row_mask, dz_flags)
         self._call("spmm_normbwd_rows" if row_mask is not None else "spmm_normbwd", _lib.load().tagrec_spmm_normbwd_sparse_f32,
                    self._h, _lib.ptr(g_in), _lib.ptr(in_flags),
                    _lib.ptr(in_count), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p),
@@ -475,11 +546,8 @@ class Graph:
     def spmm_axpy_sparse(self, g_in, in_flags, in_count, b, b_scale, g_out, row_mask=None, b_flags=None):
         """row_mask: rows whose byte is 0 are not touched (the caller knows their result and has written it).
         b_flags: rows of `b` whose byte is 0 are zero and are not read."""
-        D = self._chk_x(g_in, self.shape[1], "spmm_axpy g_in")
-        if row_mask is not None:
-            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
-            if row_mask.numel() != self.shape[0]:
-                raise _lib.TagrecError("spmm_axpy_sparse: row_mask must have one byte per row")
+        D = self._chk_x(g_in, self.shape[1], "spmm_axpy_sparse g_in")
+        self._chk_axpy_sparse(D, in_flags, in_count, b, g_out, row_mask, b_flags)
         self._call("spmm_axpy_rows" if row_mask is not None else "spmm_axpy", _lib.load().tagrec_spmm_axpy_sparse_f32, self._h,
                    _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(b), float(b_scale), _lib.ptr(g_out),
                    _lib.ptr(row_mask), _lib.ptr(b_flags), D, _lib.stream_ptr())
@@ -492,6 +560,10 @@ class Graph:
         for t, nm in ((b, "b"), (p, "p"), (m, "m"), (v, "v")):
             if self._chk_x(t, self.shape[0], "spmm_axpy_adam " + nm) != D:
                 raise _lib.TagrecError("spmm_axpy_adam: width mismatch on " + nm)
+            self._chk_dev(t, "spmm_axpy_adam " + nm)
+        self._chk_vec(in_flags, self.shape[1], torch.uint8, "spmm_axpy_adam in_flags", optional=True)
+        self._chk_count(in_count, "spmm_axpy_adam in_count")
+        self._chk_vec(b_flags, self.shape[0], torch.uint8, "spmm_axpy_adam b_flags", optional=True)
         if dev is not None:
             self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_adam_graph_f32, self._h, _lib.ptr(g_in), _lib.ptr(in_flags),
                        _lib.ptr(in_count), _lib.ptr(b), float(b_scale), _lib.ptr(b_flags), _lib.ptr(p), _lib.ptr(m), _lib.ptr(v),
@@ -506,6 +578,12 @@ class Graph:
         """g_out = A @ g_in on a row-sparse operand (in_count None: flags always consulted), row flags of the result written
         to out_flags; row_mask: only these rows are computed / written."""
         D = self._chk_x(g_in, self.shape[1], "spmm_flags g_in")
+        self._chk_w(g_out, self.shape[0], D, "spmm_flags g_out")
+        self._chk_vec(in_flags, self.shape[1], torch.uint8, "spmm_flags in_flags", optional=True)
+        self._chk_count(in_count, "spmm_flags in_count")
+        self._chk_vec(out_flags, self.shape[0], torch.uint8, "spmm_flags out_flags", optional=True)
+        self._chk_count(out_count, "spmm_flags out_count")
+        self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_flags row_mask", optional=True)
         self._call("spmm_flags_rows" if row_mask is not None else "spmm_flags", _lib.load().tagrec_spmm_flags_f32, self._h,
                    _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(g_out), _lib.ptr(out_flags),
                    _lib.ptr(out_count), _lib.ptr(row_mask), D, _lib.stream_ptr())
@@ -595,7 +673,8 @@ class EdgeDropView:
         D = self._width(X, self.shape[1], "spmm X")
         if out is None:
             out = torch.empty(self.shape[0], D, dtype=torch.float32, device=X.device)
-        self.base._chk_x(out, self.shape[0], "spmm out")
+        self.base._chk_w(out, self.shape[0], D, "spmm out")
+        self.base._chk_dev(X, "spmm X")
         self.base._call("spmm", _lib.load().tagrec_spmm_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(out), *self._ed(), D,
                         _lib.stream_ptr())
         return out
@@ -604,18 +683,23 @@ class EdgeDropView:
         self.spmm_norm_acc_rows(X, y_raw, inv_norm, acc, acc_scale, None, drop_p, seed)
 
     def spmm_norm_acc_rows(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, drop_p=0.0, seed=0):
-        D = self._width(X, self.shape[1], "spmm_norm_acc X")
+        D = self._width(X, self.shape[1], "spmm_norm_acc_rows X")
+        self.base._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
         self.base._call("spmm_norm_acc_rows" if row_mask is not None else "spmm_norm_acc",
                         _lib.load().tagrec_spmm_norm_acc_rows_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(y_raw), _lib.ptr(inv_norm),
                         _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), *self._ed(), D,
                         _lib.stream_ptr())
 
     def spmm_listed(self, rows, X, out=None):
-        rows = rows.contiguous()
+        rows = self.base._chk_rows(rows, "spmm_listed rows")
         lib = _lib.load()
         D = self._width(X, self.shape[1], "spmm_listed X")
+        self.base._chk_dev(X, "spmm_listed X")
         if out is None:
             out = torch.empty(rows.numel(), D, dtype=torch.float32, device=X.device)
+        self.base._chk_w(out, rows.numel(), D, "spmm_listed out")
+        if rows.numel() == 0:
+            return out
         ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), D)
         ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
         self.base._call("spmm_listed", lib.tagrec_spmm_listed_edrop_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
@@ -627,14 +711,8 @@ class EdgeDropView:
 
     def spmm_normbwd_sparse(self, g_in, in_flags, in_count, x_raw, inv_norm, dz, d_scale, g_out, out_flags, out_count,
                             drop_p=0.0, seed=0, row_mask=None, dz_flags=None):
-        D = self._width(g_in, self.shape[1], "spmm_normbwd g_in")
-        for t, nm in ((x_raw, "x_raw"), (dz, "dz"), (g_out, "g_out")):
-            if self.base._chk_x(t, self.shape[0], "spmm_normbwd " + nm) != D:
-                raise _lib.TagrecError("spmm_normbwd: width mismatch on " + nm)
-        if row_mask is not None:
-            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
-            if row_mask.numel() != self.shape[0]:
-                raise _lib.TagrecError("spmm_normbwd_sparse: row_mask must have one byte per row")
+        D = self._width(g_in, self.shape[1], "spmm_normbwd_sparse g_in")
+        self.base._chk_normbwd_sparse(D, in_flags, in_count, x_raw, inv_norm, dz, g_out, out_flags, out_count, row_mask, dz_flags)
         self.base._call("spmm_normbwd_rows" if row_mask is not None else "spmm_normbwd",
                         _lib.load().tagrec_spmm_normbwd_sparse_edrop_f32, self.handle, _lib.ptr(g_in), _lib.ptr(in_flags),
                         _lib.ptr(in_count), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p),
@@ -645,14 +723,8 @@ class EdgeDropView:
         self.spmm_axpy_sparse(g_in, None, None, b, b_scale, g_out)
 
     def spmm_axpy_sparse(self, g_in, in_flags, in_count, b, b_scale, g_out, row_mask=None, b_flags=None):
-        D = self._width(g_in, self.shape[1], "spmm_axpy g_in")
-        for t, nm in ((b, "b"), (g_out, "g_out")):
-            if self.base._chk_x(t, self.shape[0], "spmm_axpy " + nm) != D:
-                raise _lib.TagrecError("spmm_axpy: width mismatch on " + nm)
-        if row_mask is not None:
-            _lib.require_gpu_tensor(row_mask, torch.uint8, "row_mask")
-            if row_mask.numel() != self.shape[0]:
-                raise _lib.TagrecError("spmm_axpy_sparse: row_mask must have one byte per row")
+        D = self._width(g_in, self.shape[1], "spmm_axpy_sparse g_in")
+        self.base._chk_axpy_sparse(D, in_flags, in_count, b, g_out, row_mask, b_flags)
         self.base._call("spmm_axpy_rows" if row_mask is not None else "spmm_axpy", _lib.load().tagrec_spmm_axpy_sparse_edrop_f32,
                         self.handle, _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(b), float(b_scale),
                         _lib.ptr(g_out), _lib.ptr(row_mask), _lib.ptr(b_flags), *self._ed(), D, _lib.stream_ptr())

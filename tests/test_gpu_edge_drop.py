@@ -20,28 +20,11 @@ pytestmark = pytest.mark.gpu
 
 import tagrec_amd as T
 from tagrec_amd import graph as G, help as H
+from spmm_ref import edge_kept as np_mask          # the numpy restatement of the mask
 
 DEV = torch.device("cuda:0")
 ACT = dict(rtol=1e-5, atol=1e-6)
 GRAD = dict(rtol=1e-3, atol=1e-6)
-U64 = np.uint64
-
-
-# ------------------------------------------------------------------------------------------- numpy restatement of the mask
-def mix64(z):
-    with np.errstate(over="ignore"):
-        z = z + U64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> U64(30))) * U64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> U64(27))) * U64(0x94D049BB133111EB)
-        return z ^ (z >> U64(31))
-
-
-def np_mask(rows, cols, p, seed, transposed=False):
-    i, j = (cols, rows) if transposed else (rows, cols)
-    key = (i.astype(U64) << U64(32)) | (j.astype(U64) & U64(0xFFFFFFFF))
-    h = mix64(U64(seed) ^ mix64(key))
-    thr = U64(int(np.float32(p) * np.float32(16777216.0)))
-    return (h >> U64(40)) >= thr
 
 
 # ------------------------------------------------------------------------------------------------------------- fixtures

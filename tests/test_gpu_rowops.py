@@ -25,77 +25,18 @@ from tagrec_amd import _lib, help as H, rowops, train_data
 from tagrec_amd.dist import HipOps
 from tagrec_amd.rowops import VEC_WIDTHS
 
+from spmm_ref import U32, Chk, f64 as _f64, norm_rows as _norm_rows, np_drop, randn as _randn, ref_norm_bwd as _ref_norm_bwd, \
+    same_bits as _same_bits
+
 DEV = torch.device("cuda:0")
 OPS = HipOps()
-U32 = 2.0 ** -24                       # unit roundoff of fp32
-U64 = np.uint64
 SCALAR_WIDTHS = (4, 12, 48, 100, 260)  # below a wave .. more than one trip of the scalar kernels' lane loop
 WIDTHS = VEC_WIDTHS + SCALAR_WIDTHS
 ROW_COUNTS = (1, 127, 129, 1031)       # around the vector kernel's rows per block (128 at D = 8, 4 at D = 256)
 S = float(np.float32(1.0 / 3.0))       # a scale that is exact as the float the ABI takes
 
 
-# ------------------------------------------------------------------------------------------------------------ the helper
-def _f64(t):
-    return t.detach().cpu().double().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
-
-
-class Chk:
-    """Collects err / bound of every comparison of one test; `done()` prints the worst and asserts it is <= 1."""
-
-    def __init__(self, name):
-        self.name, self.worst, self.where = name, 0.0, "-"
-
-    def close(self, what, got, ref, mag, c, extra=0.0):
-        got, ref = _f64(got), _f64(ref)
-        assert got.shape == ref.shape, f"{what}: shape {got.shape} vs {ref.shape}"
-        assert np.isfinite(got).all() and np.isfinite(ref).all(), f"{what}: non-finite value"
-        bound = np.broadcast_to(c * U32 * _f64(mag) + extra + 1e-30, ref.shape)
-        ratio = np.abs(got - ref) / bound
-        if ratio.size and ratio.max() > self.worst:
-            i = np.unravel_index(int(ratio.argmax()), ratio.shape)
-            self.worst = float(ratio.max())
-            self.where = f"{what}{list(map(int, i))}: got {got[i]!r} ref {ref[i]!r} bound {bound[i]:.3e}"
-
-    def done(self):
-        print(f"[rowops] {self.name}: worst err/bound = {self.worst:.3f}  ({self.where})")
-        assert self.worst <= 1.0, f"{self.name}: err / bound = {self.worst:.3f} at {self.where}"
-
-
-def _randn(*shape, seed, scale=0.1):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 # ====================================================================================================== row normalise
-def _norm_rows(n, D, seed):
-    """x, dz [n, D] with, by row index mod 8: 1 an all-zero x row, 3 an x row of norm ~1e-13 (clamped, non-zero), 5 an all-zero
-    dz row, 6 a dz row that is zero but for one -0.0; the others ordinary.  -> x, dz, clamped (fp64 norm below eps)."""
-    x, dz = _randn(n, D, seed=seed), _randn(n, D, seed=seed + 1)
-    r = torch.arange(n) % 8
-    x[r == 1] = 0
-    tiny = r == 3
-    x[tiny] = x[tiny] / x[tiny].double().norm(dim=1, keepdim=True).float() * 1e-13
-    dz[r == 5] = 0
-    dz[r == 6] = 0
-    dz[r == 6, D // 2] = -0.0
-    clamped = (x.double().norm(dim=1) < 1e-12).numpy()
-    return x, dz, clamped
-
-
-def _ref_norm_bwd(x, inv, dz, s, clamped):
-    """fp64 normalize-backward from the kernel's own inputs (x, inv, dz): inv (s dz - z (z . s dz)), z = x inv, and the dot
-    dropped where the norm was clamped to eps (the denominator is then a constant).  -> ref, mag, dot, dot_mag."""
-    x, inv, sdz = _f64(x), _f64(inv)[:, None], s * _f64(dz)
-    z = x * inv
-    dot, dmag = (z * sdz).sum(1, keepdims=True), np.abs(z * sdz).sum(1, keepdims=True)
-    dot[clamped], dmag[clamped] = 0.0, 0.0
-    return inv * (sdz - z * dot), np.abs(inv) * (np.abs(sdz) + np.abs(z) * dmag), dot[:, 0], dmag[:, 0]
-
-
 def test_fp64_normalize_backward_formula_is_torch_autograd():
     """The reference of the backward tests (above) is F.normalize's autograd in fp64, clamped rows included."""
     x, dz, clamped = _norm_rows(64, 12, seed=3)
@@ -551,24 +492,6 @@ def test_transtag_batch_loss(D, B, margin):
 
 
 # ==================================================================================================== message dropout
-def mix64(z):
-    with np.errstate(over="ignore"):
-        z = z + U64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> U64(30))) * U64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> U64(27))) * U64(0x94D049BB133111EB)
-        return z ^ (z >> U64(31))
-
-
-def np_drop(x, idx4, p, seed):
-    """numpy restatement of drop4: x [..., 4] float32, idx4 the float4 index of each group of four."""
-    p32 = np.float32(p)
-    h = mix64(U64(seed) ^ mix64(idx4.astype(U64)))
-    thr = U64(int(p32 * np.float32(65536.0)))
-    keep = np.float32(1.0) / (np.float32(1.0) - p32)
-    draws = np.stack([(h >> U64(s)) & U64(0xFFFF) for s in (0, 16, 32, 48)], -1)
-    return np.where(draws >= thr, x * keep, np.float32(0.0)).astype(np.float32)
-
-
 DROP_N4 = 1048576 + 5                   # float4 elements: five more than the 4096 x 256 threads of the capped grid
 SEEDS = (1, 2, (2020 << 24) + 1)
 

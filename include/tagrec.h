@@ -428,6 +428,24 @@ int tagrec_eval_topk_auc_f32(const float* U, const float* I, int64_t n_item, int
 int tagrec_sample_negative_i64(const int64_t* left, int64_t n_rows, const int64_t* rowptr, const int32_t* cols,
                                int64_t n_left, int64_t n_right, uint64_t seed, int64_t* neg, void* stream);
 
+/* The same sampler with a choice of proposal and n_cand candidates per row (not in the reference, which draws uniformly).
+ * With mix64 = the splitmix64 finaliser and base_0 = mix64(seed ^ mix64(e)), candidate c of row e runs the rejection loop
+ * above (at most 4096 tries, the last one kept) on the stream base_c = base_0 for c = 0, mix64(base_0 + (c << 32)) else:
+ *   uniform (alias_prob == NULL): try t draws umul64hi(mix64(base_c + t), n_right) -- candidate 0 is the draw of
+ *     tagrec_sample_negative_i64;
+ *   alias table (alias_prob float32 [n_right], alias_idx int32 [n_right], Vose): j = umul64hi(mix64(base_c + 2t), n_right),
+ *     u = float(mix64(base_c + 2t + 1) >> 40) * 2^-24; the draw is j if u < alias_prob[j], else alias_idx[j].
+ * Candidates are drawn with replacement.  n_cand == 1: neg[e] = candidate 0, no table is read (U, I, ld, D are ignored;
+ * score_out must be NULL).  n_cand in 2 .. 16: score_c = sum_k U[left[e] * ld_u + k] * I[cand_c * ld_i + k] in fp32 and
+ * neg[e] = the first arg-max in c order (a later candidate wins only with a strictly greater score: ties keep the
+ * lowest c, a NaN score never replaces an earlier candidate).  D % 4 == 0, 8 <= D <= 1024, ld % 4 == 0, ld >= D, 16-byte
+ * aligned tables; U must hold n_left rows and I n_right rows.  cand_out int64 [n_rows, n_cand] and score_out float32
+ * [n_rows, n_cand] are optional.  A pure function of its arguments: no atomics, two launches give the same bits. */
+int tagrec_sample_negative_ex_i64(const int64_t* left, int64_t n_rows, const int64_t* rowptr, const int32_t* cols,
+                                  int64_t n_left, int64_t n_right, uint64_t seed, int n_cand, const float* alias_prob,
+                                  const int32_t* alias_idx, const float* U, int64_t ld_u, const float* I, int64_t ld_i,
+                                  int D, int64_t* neg, int64_t* cand_out, float* score_out, void* stream);
+
 /* ---- TransTag phase of TGCN (tgcn.py:251-261, loss.py:35-41, 27-32) on the EGO tables -------------------------
  * quad: int64 [B,4] = (user, tag, pos_item, neg_item).  fwd: loss_out[0] = mean relu(margin + ||u+t-p|| - ||u+t-n||),
  * loss_out[1] = l2reg_loss(u, t, p, n) (unweighted); dist [B,2] keeps the two distances; partials: 2*ceil(B/4) floats.

@@ -175,6 +175,9 @@ _SIGNATURES = {
     "tagrec_eval_topk_auc_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_sample_negative_i64": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p],
+    "tagrec_sample_negative_ex_i64": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p],
     "tagrec_transtag_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_void_p, c_void_p,
                                 c_void_p, c_void_p],
     "tagrec_transtag_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_void_p, c_void_p,

@@ -20,7 +20,13 @@ _BASE = {
     "hip_graph": False,       # Basic_train: replay each phase's step as one captured HIP graph (train.GraphedStep)
     "deterministic": False,   # LightGCN / NGCF: fold batch gradients in a fixed order (rowops.scatter_rows_ordered), no float atomics
     "all_gather": "collective",   # row-sharded models (dist.py): "direct" = one grouped send / receive pair per peer
+    # negative sampler of the BPR producers (train_data.py; the reference has the uniform proposal and one draw only)
+    "neg_sampling": "uniform",    # "popularity": proposal proportional to (distinct train users of the item) ** neg_pop_alpha
+    "neg_pop_alpha": 0.75,
+    "neg_candidates": 1,          # > 1: draw that many candidates, keep the one the current model scores highest
 }
+NEG_SAMPLING_MODES = ("uniform", "popularity")
+MAX_NEG_CANDIDATES = 16
 
 # utility/config.py:1-12, 41-52
 _PER_MODEL = {
@@ -46,7 +52,21 @@ def get_config(model="lightgcn", **overrides):
     cfg.update(_PER_MODEL[model])
     cfg["device"] = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     cfg.update(overrides)
+    check_neg_sampling(cfg)
     return cfg
+
+
+def check_neg_sampling(cfg):
+    """The three sampler keys of a config -> (mode, alpha, candidates); an unknown value is refused."""
+    from ._lib import TagrecError
+    mode, alpha, cand = cfg.get("neg_sampling", "uniform"), cfg.get("neg_pop_alpha", 0.75), cfg.get("neg_candidates", 1)
+    if mode not in NEG_SAMPLING_MODES:
+        raise TagrecError(f"unknown neg_sampling {mode!r} (have {NEG_SAMPLING_MODES})")
+    if isinstance(cand, bool) or not isinstance(cand, int) or not 1 <= cand <= MAX_NEG_CANDIDATES:
+        raise TagrecError(f"neg_candidates must be an integer in 1 .. {MAX_NEG_CANDIDATES}, got {cand!r}")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not alpha == alpha or abs(alpha) == float("inf"):
+        raise TagrecError(f"neg_pop_alpha must be a finite number, got {alpha!r}")
+    return mode, float(alpha), cand
 
 
 CFG = get_config("lightgcn")

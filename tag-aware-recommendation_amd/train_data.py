@@ -13,12 +13,41 @@ list, re-draw until a non-positive comes up; then a device-side shuffle.
 Same distribution (one uniform non-train item per train edge); the reference's
 own stream is not reproducible from its seed, so parity runs use
 `Fixed_training_data` with arrays shared by both sides.
+
+Beyond the reference (config keys `neg_sampling`, `neg_pop_alpha`, `neg_candidates`; csrc/sampler.hip): a
+popularity-weighted proposal through an alias table, and dynamic hard negatives -- several candidates per edge, of
+which the one the current model scores highest is kept.  The defaults give the uniform stream above bit for bit.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .config import CFG as _GLOBAL_CFG
+from .config import CFG as _GLOBAL_CFG, check_neg_sampling
+
+
+def alias_table(weights):
+    """Vose's alias method on the host in float64: weights [n] -> (prob float32 [n], alias int32 [n]).  Column j is drawn
+    uniformly and kept with probability prob[j], else alias[j] is taken, so id i comes up with probability
+    (prob[i] + sum over j with alias[j] == i of (1 - prob[j])) / n = w_i / sum(w).  Deterministic, O(n); a zero weight gets
+    prob 0 and is nobody's alias, so it is never drawn."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0) or not w.sum() > 0:
+        raise _lib.TagrecError("alias_table: weights must be finite, non-negative and not all zero")
+    n = w.size
+    p = w * (n / w.sum())
+    prob = np.ones(n, dtype=np.float64)
+    alias = np.arange(n, dtype=np.int64)
+    # two stacks; the zero weights are popped first, while columns with mass to give are certain to be left
+    small = [int(i) for i in np.flatnonzero((p < 1.0) & (w > 0))] + [int(i) for i in np.flatnonzero(w == 0)]
+    large = [int(i) for i in np.flatnonzero(p >= 1.0)]
+    p = p.tolist()
+    while small and large:
+        s, l = small.pop(), large.pop()
+        prob[s], alias[s] = p[s], l
+        p[l] = (p[l] + p[s]) - 1.0
+        (small if p[l] < 1.0 else large).append(l)
+    # what is left on either stack is 1 up to rounding: the column keeps itself
+    return prob.astype(np.float32), alias.astype(np.int32)
 
 
 class Abstract_training_data:
@@ -57,18 +86,88 @@ class _Positives:
         self.cols = (key - l * n_right).to(torch.int32).contiguous()
         self.n_left, self.n_right = int(n_left), int(n_right)
 
-    def sample(self, left, seed):
-        """One uniform non-positive draw per entry of `left` (HIP kernel, counter-based generator)."""
+    def sample(self, left, seed, n_cand=1, alias=None, user_table=None, item_table=None, return_candidates=False):
+        """One non-positive draw per entry of `left` (HIP kernel, counter-based generator).  Defaults: the uniform draw.
+        alias = (prob float32 [n_right], alias int32 [n_right]) on the device: draws follow that alias table instead.
+        n_cand > 1: that many candidates per entry, the one with the highest user_table[left] . item_table[candidate]
+        is returned (first arg-max; float32 tables [n_left, D] / [n_right, D], row views of wider tensors allowed).
+        return_candidates: -> (neg, candidates int64 [n, n_cand], scores float32 [n, n_cand] or None when n_cand == 1)."""
         left = left.contiguous()
         neg = torch.empty_like(left)
-        _lib.check(_lib.load().tagrec_sample_negative_i64(_lib.ptr(left), left.numel(), _lib.ptr(self.rowptr),
-                                                          _lib.ptr(self.cols), self.n_left, self.n_right, int(seed),
-                                                          _lib.ptr(neg), _lib.stream_ptr()), "sample_negative")
-        return neg
+        if left.numel() == 0:                     # (an empty tensor has no device pointer to hand over)
+            n_cand = int(n_cand)
+            return (neg, neg.new_empty((0, n_cand)), None if n_cand == 1 else neg.new_empty((0, n_cand), dtype=torch.float32)) \
+                if return_candidates else neg
+        if n_cand == 1 and alias is None and not return_candidates:
+            _lib.check(_lib.load().tagrec_sample_negative_i64(_lib.ptr(left), left.numel(), _lib.ptr(self.rowptr),
+                                                              _lib.ptr(self.cols), self.n_left, self.n_right, int(seed),
+                                                              _lib.ptr(neg), _lib.stream_ptr()), "sample_negative")
+            return neg
+        prob = idx = None
+        if alias is not None:
+            prob = _lib.require_gpu_tensor(alias[0], torch.float32, "sample: alias prob")
+            idx = _lib.require_gpu_tensor(alias[1], torch.int32, "sample: alias ids")
+            if prob.shape != (self.n_right,) or idx.shape != (self.n_right,):
+                raise _lib.TagrecError(f"sample: the alias table must hold {self.n_right} columns")
+        U = I = None
+        ld_u = ld_i = D = 0
+        if n_cand != 1:
+            U, ld_u = self._table(user_table, self.n_left, "user_table")
+            I, ld_i = self._table(item_table, self.n_right, "item_table")
+            D = U.shape[1]
+            if I.shape[1] != D:
+                raise _lib.TagrecError(f"sample: user_table has {D} columns, item_table {I.shape[1]}")
+        cand = torch.empty((left.numel(), n_cand), dtype=torch.int64, device=left.device) if return_candidates else None
+        score = torch.empty((left.numel(), n_cand), dtype=torch.float32, device=left.device) \
+            if return_candidates and n_cand != 1 else None
+        _lib.check(_lib.load().tagrec_sample_negative_ex_i64(
+            _lib.ptr(left), left.numel(), _lib.ptr(self.rowptr), _lib.ptr(self.cols), self.n_left, self.n_right, int(seed),
+            int(n_cand), _lib.ptr(prob), _lib.ptr(idx), _lib.ptr(U), ld_u, _lib.ptr(I), ld_i, D, _lib.ptr(neg), _lib.ptr(cand),
+            _lib.ptr(score), _lib.stream_ptr()), "sample_negative_ex")
+        return (neg, cand, score) if return_candidates else neg
+
+    @staticmethod
+    def _table(t, n_rows, name):
+        """A scoring table for the kernel -> (tensor, row stride in floats): a float32 GPU matrix with unit column stride
+        and exactly n_rows rows; the kernel itself checks width, stride and alignment."""
+        if t is None:
+            raise _lib.TagrecError(f"sample: n_cand > 1 needs {name}")
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[0] >= 1 and t.stride(1) == 1:
+            _lib.require_gpu_tensor(t[0], torch.float32, f"sample: {name}")      # (a row view is itself not contiguous)
+        else:
+            t = _lib.require_gpu_tensor(t, torch.float32, f"sample: {name}")
+        if t.dim() != 2 or t.shape[0] != n_rows:
+            raise _lib.TagrecError(f"sample: {name} must be [{n_rows}, D], got {list(t.shape)}")
+        return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+    def popularity_alias(self, alpha):
+        """Alias table (device tensors) of the proposal w_i = deg_i ** alpha, deg_i = distinct left ids of right id i.
+        Ids nobody holds get weight 0.  A left id whose positives are the whole support could never be given a
+        negative: refused."""
+        deg = torch.bincount(self.cols.long(), minlength=self.n_right).cpu().numpy().astype(np.float64)
+        w = np.where(deg > 0, np.power(np.maximum(deg, 1.0), float(alpha)), 0.0)
+        prob, idx = alias_table(w)
+        support = int(np.count_nonzero(w > 0))
+        longest = int((self.rowptr[1:] - self.rowptr[:-1]).max()) if self.n_left else 0
+        if longest >= support:
+            raise _lib.TagrecError(f"neg_sampling='popularity': a left id holds all {support} ids of non-zero weight, "
+                                   "no negative can be drawn for it")
+        dev = self.cols.device
+        return torch.from_numpy(prob).to(dev), torch.from_numpy(idx).to(dev)
+
+
+def _sampler_keys(cfg, pos):
+    """(alias table or None, number of candidates) of a producer, from the config's sampler keys."""
+    mode, alpha, n_cand = check_neg_sampling(cfg)
+    return (pos.popularity_alias(alpha) if mode == "popularity" else None), n_cand
 
 
 class BPR_training_data(Abstract_training_data):
-    def __init__(self, data, args=None, config=None, seed=None):
+    """One negative per train edge, re-drawn and shuffled every epoch.  With config["neg_candidates"] > 1 the epoch's
+    negatives are scored by `model` (given here or through `attach_model`): one eval-mode, no-grad `model.forward()` per
+    epoch supplies the user and item tables `predict_rating` scores with."""
+
+    def __init__(self, data, args=None, config=None, seed=None, model=None):
         super().__init__(args, config)
         cfg = config if config is not None else _GLOBAL_CFG
         self.num = data.num["item"]
@@ -77,16 +176,51 @@ class BPR_training_data(Abstract_training_data):
         self.pos_inter = (pos if isinstance(pos, torch.Tensor) else torch.from_numpy(np.asarray(pos))).to(
             self.device, torch.int64)
         self._pos = _Positives(self.pos_inter[:, 0], self.pos_inter[:, 1], self.num_user, self.num)
+        self._alias, self._n_cand = _sampler_keys(cfg, self._pos)
+        self._model = model
         self._seed = int(cfg["seed"] if seed is None else seed)
         self._epoch = 0
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(self._seed)
-        self.all_train_data = self.get_all_training_data()
-        self.tot_inter = self.all_train_data.shape[0] // self.batch_size
+        self.tot_inter = self.pos_inter.shape[0] // self.batch_size
+        # hard negatives need the model: without one the first epoch waits for attach_model() + reset()
+        if self._n_cand == 1 or model is not None:
+            self.all_train_data = self.get_all_training_data()
+
+    def attach_model(self, model):
+        """The model whose tables score the candidates (neg_candidates > 1); takes effect at the next reset()."""
+        self._model = model
+        return self
+
+    def _score_tables(self):
+        """The propagated (user, item) tables of the attached model: eval mode, no gradient, training flag restored."""
+        m = self._model
+        if m is None:
+            raise _lib.TagrecError("BPR_training_data: neg_candidates > 1 scores candidates with the model -- pass model= "
+                                   "or call attach_model(model) before reset()")
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                out = m.forward()
+        finally:
+            m.train(was_training)
+        tabs = out[:2] if isinstance(out, (tuple, list)) else ()
+        if len(tabs) != 2 or not all(isinstance(t, torch.Tensor) and t.dim() == 2 for t in tabs) \
+                or tabs[0].shape[0] != self.num_user or tabs[1].shape[0] != self.num or tabs[0].shape[1] != tabs[1].shape[1]:
+            raise _lib.TagrecError(f"BPR_training_data: neg_candidates > 1 needs a model whose forward() returns the full "
+                                   f"[{self.num_user}, D] and [{self.num}, D] tables ({type(m).__name__} does not; sharded "
+                                   "models are not covered) -- see model= / attach_model")
+        return tabs
 
     def get_all_training_data(self):
         u, i = self.pos_inter[:, 0].contiguous(), self.pos_inter[:, 1]
-        neg = self._pos.sample(u, (self._seed << 20) + self._epoch)      # a fresh stream every epoch
+        seed = (self._seed << 20) + self._epoch                          # a fresh stream every epoch
+        if self._n_cand == 1:
+            neg = self._pos.sample(u, seed, alias=self._alias)
+        else:
+            ut, it = self._score_tables()
+            neg = self._pos.sample(u, seed, n_cand=self._n_cand, alias=self._alias, user_table=ut, item_table=it)
         self._epoch += 1
         data = torch.stack([u, i, neg], dim=1)
         perm = torch.randperm(data.shape[0], device=self.device, generator=self._gen)
@@ -109,6 +243,10 @@ class DGCF_training_data(Abstract_training_data):
         pos = data.edge_index["train"]
         pos = (pos if isinstance(pos, torch.Tensor) else torch.from_numpy(np.asarray(pos))).to(self.device, torch.int64)
         self._pos = _Positives(pos[:, 0], pos[:, 1], self.num_user, self.num_item)
+        self._alias, n_cand = _sampler_keys(cfg, self._pos)
+        if n_cand != 1:
+            raise _lib.TagrecError("DGCF_training_data: neg_candidates > 1 is not covered (it would cost a propagation per "
+                                   "mini-batch); the per-epoch producer BPR_training_data has it")
         deg = self._pos.rowptr[1:] - self._pos.rowptr[:-1]
         self._users = torch.nonzero(deg > 0).flatten()                 # keys of user_items['train']
         self.tot_inter = pos.shape[0] // self.batch_size + 1
@@ -128,7 +266,7 @@ class DGCF_training_data(Abstract_training_data):
         r = torch.rand(B, device=self.device, generator=self._gen)
         at = torch.minimum(lo + (r * (hi - lo)).long(), hi - 1)
         pos_i = self._pos.cols[at].long()
-        neg_i = self._pos.sample(u, (self._seed << 20) + self._draws)
+        neg_i = self._pos.sample(u, (self._seed << 20) + self._draws, alias=self._alias)
         self._draws += 1
         cor = [torch.randperm(n, device=self.device, generator=self._gen)[:self.cor_batch]
                for n in ([self.num_user, self.num_item] + ([self.num_tag] if self.use_tag else []))]

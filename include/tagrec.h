@@ -39,6 +39,7 @@ extern "C" {
 
 #define TAGREC_LOSS_SOFTPLUS 0    /* mean softplus(neg - pos)        (loss.py:11) */
 #define TAGREC_LOSS_LOGSIGMOID 1  /* -mean logsigmoid(pos - neg)     (loss.py:9)  */
+#define TAGREC_LOSS_SOFTMAX 2     /* sampled softmax over (pos, K negatives): tagrec_rank_fwd_f32 only */
 
 #define TAGREC_ABI_VERSION 2
 
@@ -324,6 +325,34 @@ int tagrec_bpr_bwd_f32(const float* U, const float* I, int64_t ld, int D,
                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
                        const int64_t* trip, int64_t B, const float* coef, const float* g, float reg,
                        float* dU, float* dI, float* dUreg, float* dIreg, void* stream);
+
+/* ---- Multi-negative ranking losses on COMPACT (already gathered) rows: sampled softmax, K-negative BPR ----
+ * A batch of B tuples (user, positive, K negatives), K in 1 .. 63 (the K + 1 scores of a tuple sit one per lane of a
+ * wavefront).  Ub [B, D]: the user rows; Ib [(1 + K) B, D]: item j of tuple b is row j B + b, j = 0 the positive; both
+ * with row stride ld floats.  Ureg [B, Dreg] / Ireg [(1 + K) B, Dreg] (stride ldreg): the rows the L2 term reads, in the
+ * same slot order (both NULL: no L2 term).  No index array is read: no two slots share a row.
+ * Scores s_j = Ub[b] . Ib[j B + b];  loss_b by loss_kind:
+ *   TAGREC_LOSS_SOFTMAX                 logsumexp_j(s_j / temperature) - s_0 / temperature  (maximum subtracted)
+ *   TAGREC_LOSS_SOFTPLUS / _LOGSIGMOID  mean over k = 1 .. K of the triplet loss's per-pair expression of (s_0, s_k),
+ *                                       softplus's gradient pass-through past 20 included (temperature is not read)
+ * fwd writes loss_out[0] = mean_b loss_b, loss_out[1] = 0.5 sum |row|^2 / B over all (2 + K) B L2 rows (unweighted), and
+ * coef [B, K + 1] = d loss_b / d s_j (1 / temperature and 1 / K folded in; entry 0 is minus the sum of the others).
+ * `partials`: scratch of 2*ceil(B/4) floats; the two-stage reduction is deterministic. */
+int tagrec_rank_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                        int64_t B, int K, int loss_kind, float temperature,
+                        float* coef, float* partials, float* loss_out, void* stream);
+/* bwd STORES (no atomics, no read of the old contents; a pure function of its inputs) every row of
+ *   dUb[b]       = g0 / B * sum_j coef[b, j] * Ib[j B + b]     (ascending j)
+ *   dIb[j B + b] = g0 / B * coef[b, j] * Ub[b]
+ *   dXreg[row]   = g1 / B * Xreg[row]                          for the (2 + K) B L2 rows
+ * g = device pointer to two floats (upstream gradients of the two loss parts) or NULL for (1, 1).  dUb = dIb = NULL runs
+ * the L2 part only.  dUreg = dUb and dIreg = dIb (one buffer for both parts) is allowed when Ureg = Ub, Ireg = Ib with
+ * the same stride and width: each row then receives the sum of its two terms in one store. */
+int tagrec_rank_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                        int64_t B, int K, const float* coef, const float* g,
+                        float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
 
 /* ---- N4: propagation with dynamic per-factor edge weights (DGCF model/dgcf.py:70-110, DisenGCN model/disengcn.py:23-46) --
  * The graph handle supplies the STRUCTURE (rowptr / colidx; its values are not read).  K factors own the column

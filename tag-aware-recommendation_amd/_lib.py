@@ -14,6 +14,7 @@ ABI_VERSION = 2
 
 LOSS_SOFTPLUS = 0
 LOSS_LOGSIGMOID = 1
+LOSS_SOFTMAX = 2          # the multi-negative kernels (tagrec_rank_*) only
 
 
 class TagrecError(RuntimeError):
@@ -24,6 +25,15 @@ def refuse_deterministic(config, model, not_covered):
     """Models without a fixed-order step refuse config["deterministic"] = True loudly instead of ignoring it."""
     if config.get("deterministic", False):
         raise TagrecError(f"{model}: deterministic=True is not covered (only the LightGCN and NGCF steps are): {not_covered}")
+
+
+def refuse_multi_negative(config, what):
+    """Models and producers that consume (user, positive, one negative) triplets refuse n_negatives != 1 and the "softmax"
+    loss loudly instead of training on the first negative (only the LightGCN and NGCF steps and BPR_training_data are covered)."""
+    k, loss = config.get("n_negatives", 1), config.get("mul_loss_func")
+    if k != 1 or loss == "softmax":
+        raise TagrecError(f"{what}: n_negatives={k!r} / mul_loss_func={loss!r} is not covered (multi-negative losses: the "
+                          "LightGCN and NGCF steps and BPR_training_data only); it takes n_negatives=1 and softplus / logsigmoid")
 
 
 # name -> (argtypes); every function returns int except the two noted below
@@ -60,6 +70,10 @@ _SIGNATURES = {
                            c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_bpr_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
                            c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_rank_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int,
+                            c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_rank_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_ngcf_wgrad_workspace": [c_int, c_int],
     "tagrec_ngcf_dense_fwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p],

@@ -24,9 +24,14 @@ _BASE = {
     "neg_sampling": "uniform",    # "popularity": proposal proportional to (distinct train users of the item) ** neg_pop_alpha
     "neg_pop_alpha": 0.75,
     "neg_candidates": 1,          # > 1: draw that many candidates, keep the one the current model scores highest
+    # multi-negative ranking losses (rowops.rank_fwd / rank_bwd; LightGCN, NGCF and BPR_training_data; the reference has K = 1)
+    "n_negatives": 1,             # K negatives per positive: batches are [B, 2 + K]
+    "loss_temperature": 1.0,      # tau of mul_loss_func = "softmax" (not read by the other kinds)
 }
 NEG_SAMPLING_MODES = ("uniform", "popularity")
 MAX_NEG_CANDIDATES = 16
+MUL_LOSS_FUNCS = ("softplus", "logsigmoid", "softmax")
+MAX_NEGATIVES = 63                # the kernel keeps the K + 1 scores of a tuple one per lane of a 64-lane wavefront
 
 # utility/config.py:1-12, 41-52
 _PER_MODEL = {
@@ -53,6 +58,7 @@ def get_config(model="lightgcn", **overrides):
     cfg["device"] = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     cfg.update(overrides)
     check_neg_sampling(cfg)
+    check_ranking(cfg)
     return cfg
 
 
@@ -69,7 +75,20 @@ def check_neg_sampling(cfg):
     return mode, float(alpha), cand
 
 
-CFG = get_config("lightgcn")
+def check_ranking(cfg):
+    """The three loss keys of a config -> (n_negatives, mul_loss_func, loss_temperature); a bad value is refused."""
+    from ._lib import TagrecError
+    k, loss, tau = cfg.get("n_negatives", 1), cfg.get("mul_loss_func", "softplus"), cfg.get("loss_temperature", 1.0)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_NEGATIVES:
+        raise TagrecError(f"n_negatives must be an integer in 1 .. {MAX_NEGATIVES}, got {k!r}")
+    if loss not in MUL_LOSS_FUNCS:
+        raise TagrecError(f"unknown mul_loss_func {loss!r} (have {MUL_LOSS_FUNCS})")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < float("inf"):
+        raise TagrecError(f"loss_temperature must be a finite number > 0, got {tau!r}")
+    return k, loss, float(tau)
+
+
+CFG =get_config("lightgcn")
 
 
 def init_seed(seed):

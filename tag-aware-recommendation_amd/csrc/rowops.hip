@@ -335,6 +335,132 @@ __global__ __launch_bounds__(kThreads) void bpr_bwd_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multi-negative ranking losses on COMPACT rows: tuple b = (user row b of Ub, item rows j B + b of Ib, j = 0 the positive,
+// j = 1 .. K the negatives).  One wave per tuple; lane j keeps score j = u . item_j, so K + 1 <= 64.
+//   softmax            : logsumexp_j(s_j / tau) - s_0 / tau, evaluated with the maximum subtracted
+//   softplus/logsigmoid: mean over k = 1 .. K of the triplet kernel's per-pair expression of (s_0, s_k)
+// coef[b, j] = d loss_b / d s_j (1 / tau and 1 / K folded in; entry 0 = minus the sum of the others) is all the backward
+// needs, whatever the kind.  No index array: no two slots share a row, so the backward stores, it does not add.
+constexpr int kRankHeld = 4;   // trips of the user row kept in registers (D <= 256); longer rows re-read the rest
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+
+__global__ __launch_bounds__(kThreads) void rank_fwd_kernel(const float* __restrict__ Ub, const float* __restrict__ Ib,
+                                                            int64_t ld, int D, const float* __restrict__ Ur,
+                                                            const float* __restrict__ Ir, int64_t ldr, int Dr, int64_t B,
+                                                            int K, int loss_kind, float inv_tau, float* __restrict__ coef,
+                                                            float* __restrict__ partials) {
+  __shared__ float sh[2][kThreads / kWave];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int w = threadIdx.x >> 6;
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + w;
+  float loss = 0.f, reg = 0.f;
+  if (b < B) {
+    const float* ur = Ub + b * ld;
+    float uh[kRankHeld];
+#pragma unroll
+    for (int t = 0; t < kRankHeld; ++t) uh[t] = lane + t * kWave < D ? ur[lane + t * kWave] : 0.f;
+    float s = 0.f;                                    // score `lane` of the tuple
+    for (int j = 0; j <= K; ++j) {
+      const float* ir = Ib + (static_cast<int64_t>(j) * B + b) * ld;
+      float d = 0.f;
+#pragma unroll
+      for (int t = 0; t < kRankHeld; ++t)
+        if (lane + t * kWave < D) d = fmaf(uh[t], ir[lane + t * kWave], d);
+      for (int k = lane + kRankHeld * kWave; k < D; k += kWave) d = fmaf(ur[k], ir[k], d);
+      d = wave_sum(d);
+      if (lane == j) s = d;
+    }
+    const bool neg = lane >= 1 && lane <= K;
+    const float s0 = __shfl(s, 0);
+    float c = 0.f;                                    // d loss_b / d s_lane of the negatives; the positive's entry follows
+    if (loss_kind == TAGREC_LOSS_SOFTMAX) {
+      const float z = lane <= K ? s * inv_tau : -INFINITY;
+      const float zmax = wave_max(z);
+      const float e = lane <= K ? expf(z - zmax) : 0.f;      // a weight that underflows is an exact zero
+      const float sum = wave_sum(e);                          // >= 1: the maximum contributes exp(0)
+      loss = logf(sum) + (zmax - s0 * inv_tau);
+      if (neg) c = e / sum * inv_tau;
+    } else {
+      const float inv_k = 1.0f / static_cast<float>(K);
+      float l = 0.f;
+      if (neg) {
+        const float x = s - s0;
+        l = (loss_kind == TAGREC_LOSS_LOGSIGMOID) ? neg_logsigmoid_torch(s0 - s) : softplus_torch(x);
+        // torch's softplus passes the gradient through past the threshold (see bpr_fwd_kernel)
+        c = ((loss_kind == TAGREC_LOSS_SOFTPLUS && x > 20.f) ? 1.f : 1.f / (1.f + expf(-x))) * inv_k;
+      }
+      loss = wave_sum(l) * inv_k;
+    }
+    const float c_pos = -wave_sum(c);
+    if (lane <= K) coef[b * (K + 1) + lane] = lane == 0 ? c_pos : c;
+    if (Ur) {
+      const float* a = Ur + b * ldr;
+      float ss = 0.f;
+      for (int k = lane; k < Dr; k += kWave) ss = fmaf(a[k], a[k], ss);
+      for (int j = 0; j <= K; ++j) {
+        const float* r = Ir + (static_cast<int64_t>(j) * B + b) * ldr;
+        for (int k = lane; k < Dr; k += kWave) ss = fmaf(r[k], r[k], ss);
+      }
+      reg = 0.5f * wave_sum(ss);
+    }
+  }
+  if (lane == 0) { sh[0][w] = loss; sh[1][w] = reg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float l = 0.f, g = 0.f;
+    for (int i = 0; i < kThreads / kWave; ++i) { l += sh[0][i]; g += sh[1][i]; }
+    partials[2 * blockIdx.x] = l;
+    partials[2 * blockIdx.x + 1] = g;
+  }
+}
+
+// Backward: lanes map to consecutive columns; every output row is written exactly once with plain stores.  `shared`: the L2
+// rows ARE the score rows and one gradient buffer takes both parts (dUr == dU: NGCF), so the L2 term joins the store.
+__global__ __launch_bounds__(kThreads) void rank_bwd_kernel(const float* __restrict__ Ub, const float* __restrict__ Ib,
+                                                            int64_t ld, int D, const float* __restrict__ Ur,
+                                                            const float* __restrict__ Ir, int64_t ldr, int Dr, int64_t B,
+                                                            int K, const float* __restrict__ coef, const float* __restrict__ g,
+                                                            float inv_b, float* dU, float* dI, float* dUr, float* dIr) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float g0 = (g ? g[0] : 1.f) * inv_b;
+  const float cr = (g ? g[1] : 1.f) * inv_b;
+  const bool shared = dU != nullptr && dUr == dU;
+  if (dU) {
+    const float cl = lane <= K ? g0 * coef[b * (K + 1) + lane] : 0.f;   // lane j holds (g0 / B) coef[b, j]
+    for (int k0 = 0; k0 < D; k0 += kWave) {          // (uniform trip count: the shuffles below need every lane)
+      const int k = k0 + lane;
+      const bool ok = k < D;
+      const float uv = ok ? Ub[b * ld + k] : 0.f;
+      float du = 0.f;
+      for (int j = 0; j <= K; ++j) {
+        const float c = __shfl(cl, j);
+        const int64_t at = (static_cast<int64_t>(j) * B + b) * ld + k;
+        if (ok) {
+          const float iv = Ib[at];
+          du = fmaf(c, iv, du);
+          dI[at] = shared ? fmaf(cr, iv, c * uv) : c * uv;
+        }
+      }
+      if (ok) dU[b * ld + k] = shared ? fmaf(cr, uv, du) : du;
+    }
+  }
+  if (Ur && !shared) {
+    for (int k = lane; k < Dr; k += kWave) dUr[b * ldr + k] = cr * Ur[b * ldr + k];
+    for (int j = 0; j <= K; ++j) {
+      const int64_t at = (static_cast<int64_t>(j) * B + b) * ldr;
+      for (int k = lane; k < Dr; k += kWave) dIr[at + k] = cr * Ir[at + k];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Negative sampler (train_data/utils.py:19-28 `sample_neg_item`, :31-40 `sample_neg_tail`): one uniform draw in
 // [0, n_right) per positive row, re-drawn while (left id, draw) is a positive pair.  The positives of a left id are
 // the sorted row `cols[rowptr[l] .. rowptr[l+1])`, so membership is a binary search in that row.  Counter-based
@@ -599,6 +725,47 @@ extern "C" int tagrec_bpr_bwd_f32(const float* U, const float* I, int64_t ld, in
   const int64_t blocks = (B + 3) / 4;
   bpr_bwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, static_cast<hipStream_t>(stream)>>>(
       U, I, ld, D, Ureg, Ireg, ldreg, Dreg, trip, B, coef, g, reg, 1.0f / static_cast<float>(B), dU, dI, dUreg, dIreg);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_rank_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D, const float* Ureg, const float* Ireg,
+                                   int64_t ldreg, int Dreg, int64_t B, int K, int loss_kind, float temperature, float* coef,
+                                   float* partials, float* loss_out, void* stream) {
+  TAGREC_REQUIRE(Ub && Ib && coef && partials && loss_out, "rank_fwd: null pointer");
+  TAGREC_REQUIRE(B >= 1 && D >= 1 && ld >= D, "rank_fwd: bad shape");
+  TAGREC_REQUIRE(K >= 1 && K <= 63, "rank_fwd: K must be in 1 .. 63 (one score per lane of a wavefront)");
+  TAGREC_REQUIRE((Ureg == nullptr) == (Ireg == nullptr), "rank_fwd: Ureg/Ireg must both be given or both null");
+  TAGREC_REQUIRE(!Ureg || (Dreg >= 1 && ldreg >= Dreg), "rank_fwd: bad reg shape");
+  TAGREC_REQUIRE(loss_kind == TAGREC_LOSS_SOFTPLUS || loss_kind == TAGREC_LOSS_LOGSIGMOID || loss_kind == TAGREC_LOSS_SOFTMAX,
+                 "rank_fwd: unknown loss_kind");
+  TAGREC_REQUIRE(loss_kind != TAGREC_LOSS_SOFTMAX || (temperature > 0.f && temperature <= 3.4028234e38f),
+                 "rank_fwd: the softmax temperature must be finite and > 0");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t blocks = (B + 3) / 4;
+  rank_fwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, s>>>(Ub, Ib, ld, D, Ureg, Ireg, ldreg, Dreg, B, K, loss_kind,
+                                                                      1.0f / temperature, coef, partials);
+  TAGREC_LAUNCH_CHECK();
+  bpr_reduce_kernel<<<1, kThreads, 0, s>>>(partials, blocks, 1.0f / static_cast<float>(B), loss_out);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_rank_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D, const float* Ureg, const float* Ireg,
+                                   int64_t ldreg, int Dreg, int64_t B, int K, const float* coef, const float* g, float* dUb,
+                                   float* dIb, float* dUreg, float* dIreg, void* stream) {
+  TAGREC_REQUIRE(Ub && Ib && coef, "rank_bwd: null pointer");
+  TAGREC_REQUIRE((dUb == nullptr) == (dIb == nullptr), "rank_bwd: dUb/dIb must both be given or both null (reg-only pass)");
+  TAGREC_REQUIRE(B >= 1 && D >= 1 && ld >= D, "rank_bwd: bad shape");
+  TAGREC_REQUIRE(K >= 1 && K <= 63, "rank_bwd: K must be in 1 .. 63 (one score per lane of a wavefront)");
+  TAGREC_REQUIRE(!Ureg || (Ireg && dUreg && dIreg && Dreg >= 1 && ldreg >= Dreg), "rank_bwd: bad reg arguments");
+  // one buffer for both parts: then the L2 rows must be the score rows themselves
+  TAGREC_REQUIRE(!Ureg || !dUb || ((dUreg == dUb) == (dIreg == dIb)), "rank_bwd: dUreg/dIreg must both alias dUb/dIb or neither");
+  TAGREC_REQUIRE(!Ureg || !dUb || dUreg != dUb || (Ureg == Ub && Ireg == Ib && ldreg == ld && Dreg == D),
+                 "rank_bwd: a gradient buffer shared by both parts needs Ureg = Ub and Ireg = Ib");
+  const int64_t blocks = (B + 3) / 4;
+  rank_bwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      Ub, Ib, ld, D, Ureg, Ireg, ldreg, Dreg, B, K, coef, g, 1.0f / static_cast<float>(B), dUb, dIb, dUreg, dIreg);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }

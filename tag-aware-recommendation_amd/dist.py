@@ -530,6 +530,7 @@ class ShardedLightGCN(torch.nn.Module):
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None, n_chunks=None, symmetric=None):
         super().__init__()
         _lib.refuse_deterministic(config, "ShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
+        _lib.refuse_multi_negative(config, "ShardedLightGCN")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -924,6 +925,7 @@ class ShardedNGCF(torch.nn.Module):
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None, n_chunks=None):
         super().__init__()
         _lib.refuse_deterministic(config, "ShardedNGCF", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
+        _lib.refuse_multi_negative(config, "ShardedNGCF")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -1207,6 +1209,7 @@ class FeatureShardedLightGCN(torch.nn.Module):
     def __init__(self, data, config, rowptr, col, val, n_nodes, ops=None, group=None):
         super().__init__()
         _lib.refuse_deterministic(config, "FeatureShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
+        _lib.refuse_multi_negative(config, "FeatureShardedLightGCN")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)

@@ -98,7 +98,83 @@ class _TripletLoss(torch.autograd.Function):
 
 
 def loss_kind_id(loss_func):
+    if loss_func == "softmax":
+        return _lib.LOSS_SOFTMAX
     return _lib.LOSS_LOGSIGMOID if loss_func == "logsigmoid" else _lib.LOSS_SOFTPLUS
+
+
+class _RankingLoss(torch.autograd.Function):
+    """Multi-negative ranking loss on tables + a [B, 2 + K] tuple batch: the (2 + K) B rows are gathered, the compact kernels
+    (rowops.rank_fwd / rank_bwd) run on them and the compact gradients are folded back onto the tables.
+    Returns a 2-vector: [mul_loss, l2reg_loss (unweighted)]."""
+
+    @staticmethod
+    def forward(ctx, U, I, Ureg, Ireg, tuples, loss_kind, temperature, plans):
+        for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2):
+                raise _lib.TagrecError(f"ranking_loss: {nm} must be a 2-d float32 GPU tensor")
+        tuples = _lib.require_gpu_tensor(tuples.contiguous(), torch.int64, "ranking_loss tuples")
+        if tuples.dim() != 2 or tuples.shape[1] < 3:
+            raise _lib.TagrecError(f"ranking_loss: tuples {tuple(tuples.shape)} must be [B, 2 + K]")
+        urows, irows = tuples[:, 0].contiguous(), tuples[:, 1:].t().reshape(-1)       # item j of tuple b at slot j B + b
+        Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
+        has_reg = Ureg is not None
+        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
+        Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
+        out, coef = rowops.rank_fwd(Ub, Ib, Urb, Irb, loss_kind, temperature)
+        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows, coef)
+        ctx.has_reg, ctx.same, ctx.plans = has_reg, same, plans
+        ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Ub, Ib, Urb, Irb, urows, irows, coef = ctx.saved_tensors
+        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
+        dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
+        if ctx.has_reg and ctx.same:
+            Urb, Irb, dUrb, dIrb = Ub, Ib, dUb, dIb        # reg on the same rows: one gradient buffer
+        elif ctx.has_reg:
+            dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
+        else:
+            Urb = Irb = dUrb = dIrb = None
+        rowops.rank_bwd(Ub, Ib, Urb, Irb, coef, g, dUb, dIb, dUrb, dIrb)
+
+        def fold(shape, rows, src, plan):
+            return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
+
+        dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
+        if ctx.has_reg and not ctx.same:
+            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
+        return dU, dI, None, None, None, None, None, None
+
+
+def rank_route(model, batch, n_negatives, loss_func, temperature):
+    """Which loss stage a model's step takes for `batch` [B, 2 + K]: None = the triplet kernels (K = 1 with softplus /
+    logsigmoid, exactly as before), else (K, temperature) for the multi-negative kernels.  A batch whose width disagrees with
+    the model's n_negatives is refused."""
+    if batch.dim() != 2 or batch.shape[1] != 2 + n_negatives:
+        raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit n_negatives={n_negatives} "
+                               f"(expected [B, {2 + n_negatives}] = user, positive, {n_negatives} negative(s))")
+    return (n_negatives, float(temperature)) if (n_negatives > 1 or loss_func == "softmax") else None
+
+
+def ranking_plans(tuples, n_user, n_item, width=256):
+    """(plan of the user slots, plan of the item slots) of a [B, 2 + K] tuple batch for `ranking_loss(plans=...)`: the
+    `rowops.row_list_plan`s of its B user ids over n_user rows and of its (1 + K) B item ids (slot order) over n_item rows."""
+    return (rowops.row_list_plan(tuples[:, 0].contiguous(), n_user, None, width),
+            rowops.row_list_plan(tuples[:, 1:].t().reshape(-1), n_item, None, width))
+
+
+def ranking_loss(U, I, Ureg, Ireg, tuples, loss_func, temperature=1.0, plans=None):
+    """(mul_loss, l2reg_loss) of a [B, 2 + K] batch (user, positive, K negatives; K in 1 .. 63) against user / item tables:
+    the multi-negative sibling of `triplet_loss`.  loss_func "softmax": mean_b [logsumexp_j(s_j / temperature) - s_0 /
+    temperature]; "softplus" / "logsigmoid": the mean over the B K (positive, negative) pairs of `mul_loss`'s expression.
+    l2reg_loss = 0.5 (|u|^2 + |p|^2 + sum_k |n_k|^2) / B on the rows of Ureg / Ireg (None: 0).
+    plans (`ranking_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
+    instead of by `index_add_`."""
+    out = _RankingLoss.apply(U, I, Ureg, Ireg, tuples, loss_kind_id(loss_func), float(temperature), plans)
+    return out[0], out[1]
 
 
 def triplet_loss(U, I, Ureg, Ireg, trip, loss_func):

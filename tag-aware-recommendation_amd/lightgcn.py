@@ -17,7 +17,7 @@ import torch
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG
+from .config import CFG as _GLOBAL_CFG, check_ranking
 from .graph import EdgeDropView, Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -255,8 +255,12 @@ class _PropagateBprLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active, drops=None, seed=0, restrict=True,
-                fused_opt=None, ws=None, deterministic=False):
+                fused_opt=None, ws=None, deterministic=False, rank=None):
         x0 = table.detach()
+        if rank is not None:          # (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*)
+            return _PropagateBprLoss._forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active,
+                                                   drops, seed, restrict, fused_opt, ws, deterministic, rank)
+        ctx.rank = None
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         ctx.ws, ctx.token = None, _Token()
         if ws is not None and ws.acquire(ctx.token):
@@ -288,7 +292,60 @@ class _PropagateBprLoss(torch.autograd.Function):
         return res
 
     @staticmethod
+    def _forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, tuples, loss_kind, reg_active, drops, seed, restrict,
+                      fused_opt, ws, deterministic, rank):
+        """The loss stage on `rowops.rank_fwd`: only the row list changes, T = (2 + K) B; everything around it is the triplet
+        step's.  The all-rows path gathers the T rows of `out` (the kernels take compact rows only)."""
+        ctx.rank = rank
+        ctx.fused = (table, fused_opt) if fused_opt is not None else None
+        ctx.ws, ctx.token = None, _Token()
+        if ws is not None and ws.acquire(ctx.token):
+            ctx.ws = ws
+        B, (n, D) = tuples.shape[0], x0.shape
+        ctx.reg_active, ctx.graph, ctx.B, ctx.shape = reg_active, graph, B, x0.shape
+        rows = ctx.rows = rowops.tuple_rows(tuples, n_user)
+        ctx.plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
+        ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
+                           and rows.numel() * 16 <= n)              # a batch that touches most rows gains nothing
+        if ctx.compact:
+            out_b, ctx.state = restricted_forward(graph, x0, n_layer, rows, ctx.ws)
+        else:
+            ctx.masks = {}
+            out, ctx.raws, ctx.invs = propagate_forward(graph, x0, n_layer, drops, seed, rows if restrict else None, ctx.masks)
+            ctx.drops, ctx.seed = drops, seed
+            out_b = out.index_select(0, rows)
+        ego_b = x0.index_select(0, rows)
+        res, ctx.coef = rowops.rank_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], loss_kind, rank[1])
+        ctx.out_b, ctx.ego_b = out_b, ego_b
+        return res
+
+    @staticmethod
+    def _backward_rank(ctx, g):
+        out_b, ego_b, rows, B = ctx.out_b, ctx.ego_b, ctx.rows, ctx.B
+        d_b = torch.empty_like(out_b)                                      # d / d out_b: every row is stored by the kernel
+        rowops.rank_bwd(out_b[:B], out_b[B:], None, None, ctx.coef, g, d_b[:B], d_b[B:], None, None)
+        if ctx.compact:
+            fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
+            g0 = restricted_backward(ctx.graph.transpose(), rows, d_b, ctx.state, ctx.shape, fused, ctx.ws, ctx.plan)
+            ctx.state = None
+        else:
+            d_out = rowops.fold_rows(torch.zeros(ctx.shape, dtype=torch.float32, device=out_b.device), rows, d_b, ctx.plan)
+            fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active and len(ctx.raws) >= 1) else None
+            g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
+            ctx.raws = ctx.invs = None
+        if ctx.reg_active:                                                 # L2 term on the ego rows, after the hop has written g0
+            d_e = torch.empty_like(ego_b)
+            rowops.rank_bwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctx.coef, g, None, None, d_e[:B], d_e[B:], "rank_bwd(reg)")
+            rowops.fold_rows(g0, rows, d_e, ctx.plan)
+        ctx.out_b = ctx.ego_b = None
+        if ctx.ws is not None:
+            ctx.ws.release(ctx.token)
+        return (g0,) + (None,) * 14
+
+    @staticmethod
     def backward(ctx, g):
+        if ctx.rank is not None:
+            return _PropagateBprLoss._backward_rank(ctx, g)
         if ctx.compact:
             out_b, ego_b, ctrip, rows = ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.rows
             B, D = ctrip.shape[0], out_b.shape[1]
@@ -304,7 +361,7 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.state = ctx.out_b = None
             if ctx.ws is not None:
                 ctx.ws.release(ctx.token)
-            return g0, None, None, None, None, None, None, None, None, None, None, None, None, None
+            return (g0,) + (None,) * 14
         out, x0, trip = ctx.out, ctx.x0, ctx.trip
         nu, ni = ctx.n_user, ctx.n_item
         d_out = torch.zeros_like(out)
@@ -324,7 +381,7 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.raws = ctx.invs = ctx.out = None
         if ctx.ws is not None:
             ctx.ws.release(ctx.token)
-        return g0, None, None, None, None, None, None, None, None, None, None, None, None, None
+        return (g0,) + (None,) * 14
 
 
 class LightGCN(FusedStepModel):
@@ -342,7 +399,8 @@ class LightGCN(FusedStepModel):
         self.norm_type = config["norm_type"]
         self.split_adj_k = config["split_adj_k"]
         self.reg = config["reg"]
-        self.loss_func = config["mul_loss_func"]
+        # K negatives per positive: batches are [B, 2 + K]; K > 1 or "softmax" takes the multi-negative loss kernels
+        self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
         self.node_drop = config["node_drop"]
@@ -405,6 +463,7 @@ class LightGCN(FusedStepModel):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
+        rank = H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         if self._fused_ok():
             graph = self._graph()                       # (first: kernel-mode edge dropout refuses a capture before any launch)
             drops, seed = self._drops()
@@ -412,11 +471,14 @@ class LightGCN(FusedStepModel):
             res = _PropagateBprLoss.apply(self.table, graph, self.num_layer, nu, ni, batch_data,
                                           H.loss_kind_id(self.loss_func), self.reg != 0, drops, seed, self.restrict_forward,
                                           fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None,
-                                          self.deterministic)
+                                          self.deterministic, rank)
             return res[0], self.reg * res[1]
         if self.deterministic:
             raise _lib.TagrecError("LightGCN: deterministic=True covers the fused step only (no row folds: split_adj_k == 1)")
         all_users, all_items = self.forward()[:2]
         ego = self.embed
+        if rank is not None:
+            loss, reg_loss = H.ranking_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func, rank[1])
+            return loss, self.reg * reg_loss
         loss, reg_loss = H.triplet_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func)
         return loss, self.reg * reg_loss

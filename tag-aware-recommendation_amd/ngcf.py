@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG
+from .config import CFG as _GLOBAL_CFG, check_ranking
 from .graph import Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -336,10 +336,13 @@ class _PropagateBprLoss(torch.autograd.Function):
     """(table, mats) -> [mul_loss, l2reg_loss(propagated rows)] in one autograd node."""
 
     @staticmethod
-    def forward(ctx, graph, dims, n_user, n_item, trip, loss_kind, drops, seed, fused_opt, deterministic, table, *mats):
+    def forward(ctx, graph, dims, n_user, n_item, trip, loss_kind, drops, seed, fused_opt, deterministic, rank, table, *mats):
         x0 = table.detach()
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         wps = _wps([m.detach() for m in mats])
+        ctx.rank = rank
+        if rank is not None:          # (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*)
+            return _PropagateBprLoss._forward_rank(ctx, graph, dims, n_user, trip, loss_kind, drops, seed, deterministic, x0, wps)
         B, n = trip.shape[0], x0.shape[0]
         rows = rowops.batch_rows(trip, n_user) if (RESTRICT_FORWARD or deterministic) else None
         # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
@@ -361,7 +364,46 @@ class _PropagateBprLoss(torch.autograd.Function):
         return res
 
     @staticmethod
+    def _forward_rank(ctx, graph, dims, n_user, tuples, loss_kind, drops, seed, deterministic, x0, wps):
+        """The loss stage on `rowops.rank_fwd`: only the row list changes, T = (2 + K) B.  The all-rows path gathers the T rows
+        of `out` (the kernels take compact rows only); the L2 term reads the same propagated rows."""
+        B, n = tuples.shape[0], x0.shape[0]
+        rows = ctx.rows = rowops.tuple_rows(tuples, n_user)
+        ctx.plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
+        ctx.graph, ctx.dims, ctx.B, ctx.n = graph, dims, B, n
+        ctx.compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
+                           and rows.numel() * 16 <= n)              # a batch that touches most rows gains nothing
+        if ctx.compact:
+            out_b, ctx.state = restricted_forward(graph, x0, wps, dims, rows)
+        else:
+            out, ctx.saved = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
+            out_b = out.index_select(0, rows)
+        U, I = out_b[:B], out_b[B:]
+        res, ctx.coef = rowops.rank_fwd(U, I, U, I, loss_kind, ctx.rank[1])
+        ctx.out_b = out_b
+        return res
+
+    @staticmethod
+    def _backward_rank(ctx, g):
+        out_b, B = ctx.out_b, ctx.B
+        d_b = torch.empty_like(out_b)                   # both loss parts land in one buffer; every row is stored by the kernel
+        U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
+        rowops.rank_bwd(U, I, U, I, ctx.coef, g, dU, dI, dU, dI)
+        if ctx.compact:
+            d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
+            ctx.state = None
+        else:
+            d_out = rowops.fold_rows(torch.zeros(ctx.n, out_b.shape[1], dtype=torch.float32, device=out_b.device), ctx.rows, d_b,
+                                     ctx.plan)
+            d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
+            ctx.saved = None
+        ctx.out_b = None
+        return (None,) * 11 + (d0, *_mat_grads(dws))
+
+    @staticmethod
     def backward(ctx, g):
+        if ctx.rank is not None:
+            return _PropagateBprLoss._backward_rank(ctx, g)
         if ctx.compact:
             out_b, ctrip = ctx.out_b, ctx.ctrip
             B = ctrip.shape[0]
@@ -370,7 +412,7 @@ class _PropagateBprLoss(torch.autograd.Function):
             rowops.bpr_bwd(U, I, U, I, ctrip, ctx.coef, g, dU, dI, dU, dI)
             d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
             ctx.state = ctx.out_b = None
-            return (None, None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
+            return (None,) * 11 + (d0, *_mat_grads(dws))
         out, trip, nu, ni = ctx.out, ctx.trip, ctx.nu, ctx.ni
         d_out = torch.zeros_like(out)
         U, I = out[:nu], out[nu:nu + ni]
@@ -381,7 +423,7 @@ class _PropagateBprLoss(torch.autograd.Function):
             rowops.bpr_bwd(U, I, U, I, trip, ctx.coef, g, dU, dI, dU, dI)
         d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
         ctx.saved = ctx.out = None
-        return (None, None, None, None, None, None, None, None, None, None, d0, *_mat_grads(dws))
+        return (None,) * 11 + (d0, *_mat_grads(dws))
 
 
 class NGCF(FusedStepModel):
@@ -411,7 +453,8 @@ class NGCF(FusedStepModel):
         self.norm_type = config["norm_type"]
         self.split_adj_k = config["split_adj_k"]
         self.reg = config["reg"]
-        self.loss_func = config["mul_loss_func"]
+        # K negatives per positive: batches are [B, 2 + K]; K > 1 or "softmax" takes the multi-negative loss kernels
+        self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
         self.use_tag = config["use_tag"]
         self.drop_seed = config.get("seed", 2020)
         # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
@@ -450,16 +493,20 @@ class NGCF(FusedStepModel):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
+        rank = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         if self.agg_type == "bi_agg" and self._fused_ok():
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
             res = _PropagateBprLoss.apply(self.norm_adj, tuple(self.dim_layer_list), nu, ni, batch_data,
-                                          H.loss_kind_id(self.loss_func), drops, seed, fused, self.deterministic, self.table,
-                                          *self._mats())
+                                          H.loss_kind_id(self.loss_func), drops, seed, fused, self.deterministic, rank,
+                                          self.table, *self._mats())
             return res[0], self.reg * res[1]
         if self.deterministic:
             raise _lib.TagrecError("NGCF: deterministic=True covers the fused step only (bi_agg, widths in {16, 32, 64, 128}, "
                                    "no row folds)")
         all_users, all_items = self.forward()[:2]
+        if rank is not None:
+            loss, reg_loss = H.ranking_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func, rank[1])
+            return loss, self.reg * reg_loss
         loss, reg_loss = H.triplet_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func)
         return loss, self.reg * reg_loss

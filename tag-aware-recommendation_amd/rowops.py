@@ -128,6 +128,74 @@ def batch_rows(trip, n_user):
     return torch.cat([trip[:, 0], n_user + trip[:, 1], n_user + trip[:, 2]])
 
 
+# ---- multi-negative ranking losses on compact rows (sampled softmax, K-negative BPR) ----
+
+def tuple_rows(tuples, n_user):
+    """Node ids [(2 + K) B] of a tuple batch [B, 2 + K] = (user, positive, K negatives) in the [user | item] table, in the
+    slot order of `rank_fwd`: the B users, then item j of tuple b at slot B + j B + b.  K = 1: `batch_rows`."""
+    return torch.cat([tuples[:, 0], (n_user + tuples[:, 1:]).t().reshape(-1)])
+
+
+def _rank_shape(what, Ub, Ib):
+    """(B, K) of a compact operand pair Ub [B, D] / Ib [(1 + K) B, D]."""
+    if Ub is None or Ib is None or Ub.dim() != 2 or Ib.dim() != 2:
+        raise _lib.TagrecError(f"{what}: Ub and Ib must be 2-d tensors")
+    B = Ub.shape[0]
+    K = Ib.shape[0] // B - 1 if B >= 1 else 0
+    if B < 1 or Ib.shape[0] != (1 + K) * B or not 1 <= K <= 63:
+        raise _lib.TagrecError(f"{what}: Ub {tuple(Ub.shape)} / Ib {tuple(Ib.shape)} must be [B, D] / [(1 + K) B, D] with K in 1 .. 63")
+    return B, K
+
+
+def _rank_reg_rows(what, Ureg, Ireg, B, K):
+    if Ureg is not None and Ireg is not None and (Ureg.shape[0] != B or Ireg.shape[0] != (1 + K) * B):
+        raise _lib.TagrecError(f"{what}: Ureg {tuple(Ureg.shape)} / Ireg {tuple(Ireg.shape)} must have {B} / {(1 + K) * B} rows")
+
+
+def rank_fwd(Ub, Ib, Ureg, Ireg, loss_kind, temperature=1.0):
+    """Ranking loss of B tuples on gathered rows: Ub [B, D] users, Ib [(1 + K) B, D] items (item j of tuple b at row j B + b,
+    j = 0 the positive); Ureg / Ireg: the L2 rows in the same slot order (None: no L2 term).
+    -> (res = [mul_loss, l2reg_loss (unweighted)], coef [B, K + 1] for `rank_bwd`)."""
+    B, K = _rank_shape("rank_fwd", Ub, Ib)
+    ld, D = _pair_ld("rank_fwd", ("Ub", "Ib"), Ub, Ib)
+    ldreg, dreg = _pair_ld("rank_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
+    _rank_reg_rows("rank_fwd", Ureg, Ireg, B, K)
+    coef = torch.empty(B, K + 1, dtype=torch.float32, device=Ub.device)
+    partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=Ub.device)     # two floats per launched block
+    res = torch.empty(2, dtype=torch.float32, device=Ub.device)
+    check(load().tagrec_rank_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, K, loss_kind,
+                                     float(temperature), ptr(coef), ptr(partials), ptr(res), stream_ptr()), "rank_fwd")
+    return res, coef
+
+
+def rank_bwd(Ub, Ib, Ureg, Ireg, coef, g, dUb, dIb, dUreg, dIreg, what="rank_bwd"):
+    """STORES the gradients of `rank_fwd`'s two loss parts (g = their upstream gradients, two floats; None: both 1) into every
+    row of dUb / dIb and dUreg / dIreg -- no atomics, the old contents are not read.  dUb = dIb = None: the L2 part only;
+    Ureg = Ireg = None: no L2 part; dUreg is dUb and dIreg is dIb (with Ureg is Ub, Ireg is Ib): one buffer takes the sum."""
+    B, K = _rank_shape(what, Ub, Ib)
+    g = None if g is None else g.contiguous()
+    ld, D = _pair_ld(what, ("Ub", "Ib"), Ub, Ib, (dUb, dIb))
+    ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
+    _rank_reg_rows(what, Ureg, Ireg, B, K)
+    if coef.shape != (B, K + 1) or not coef.is_contiguous():
+        raise _lib.TagrecError(f"{what}: coef {tuple(coef.shape)} must be a contiguous [{B}, {K + 1}] tensor")
+    for nm, t, n in (("dUb", dUb, B), ("dIb", dIb, (1 + K) * B), ("dUreg", dUreg, B), ("dIreg", dIreg, (1 + K) * B)):
+        if t is not None and t.shape[0] != n:
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {n} rows")
+    check(load().tagrec_rank_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, K, ptr(coef), ptr(g),
+                                     ptr(dUb), ptr(dIb), ptr(dUreg), ptr(dIreg), stream_ptr()), what)
+
+
+def fold_rows(dst, rows, src, plan=None, accumulate=True):
+    """dst[rows[j]] (+)= src[j]: through `plan` (the `row_list_plan` of rows) in a fixed order, else by `index_add_` (float
+    atomics where the list names a row twice).  Without `accumulate` the listed rows of dst are overwritten with their sums."""
+    if plan is not None:
+        return scatter_rows_ordered(dst, plan, src, accumulate)
+    if not accumulate:
+        dst.index_fill_(0, rows, 0.0)
+    return dst.index_add_(0, rows, src)
+
+
 # ---- fixed-order scatter of compact rows (csrc/rowscatter.hip): the `deterministic` mode of LightGCN / NGCF ----
 
 class RowListPlan:

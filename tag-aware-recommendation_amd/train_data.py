@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import CFG as _GLOBAL_CFG, check_neg_sampling
+from .config import CFG as _GLOBAL_CFG, check_neg_sampling, check_ranking
 
 
 def alias_table(weights):
@@ -163,7 +163,8 @@ def _sampler_keys(cfg, pos):
 
 
 class BPR_training_data(Abstract_training_data):
-    """One negative per train edge, re-drawn and shuffled every epoch.  With config["neg_candidates"] > 1 the epoch's
+    """config["n_negatives"] = K negatives per train edge (default one: [E, 3] triplets; else [E, 2 + K] tuples), re-drawn
+    and shuffled every epoch.  With config["neg_candidates"] > 1 the epoch's
     negatives are scored by `model` (given here or through `attach_model`): one eval-mode, no-grad `model.forward()` per
     epoch supplies the user and item tables `predict_rating` scores with."""
 
@@ -177,6 +178,7 @@ class BPR_training_data(Abstract_training_data):
             self.device, torch.int64)
         self._pos = _Positives(self.pos_inter[:, 0], self.pos_inter[:, 1], self.num_user, self.num)
         self._alias, self._n_cand = _sampler_keys(cfg, self._pos)
+        self._n_neg = check_ranking(cfg)[0]          # K negatives per edge: the epoch array is [E, 2 + K]
         self._model = model
         self._seed = int(cfg["seed"] if seed is None else seed)
         self._epoch = 0
@@ -213,16 +215,26 @@ class BPR_training_data(Abstract_training_data):
                                    "models are not covered) -- see model= / attach_model")
         return tabs
 
+    def negatives(self, epoch):
+        """The epoch's negatives [E, K] in edge order (before the shuffle), a pure function of (seed, epoch) and, with
+        neg_candidates > 1, of the attached model.  Column j is an independent rejection-tested draw per edge on its own
+        counter stream derived from (epoch seed, j); column 0 is the stream of n_negatives = 1."""
+        u = self.pos_inter[:, 0].contiguous()
+        seed = (self._seed << 20) + int(epoch)                           # a fresh stream every epoch
+        ut, it = self._score_tables() if self._n_cand != 1 else (None, None)
+        cols = []
+        for j in range(self._n_neg):
+            sj = (seed + j * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF    # j = 0: the epoch seed itself
+            if self._n_cand == 1:
+                cols.append(self._pos.sample(u, sj, alias=self._alias))
+            else:
+                cols.append(self._pos.sample(u, sj, n_cand=self._n_cand, alias=self._alias, user_table=ut, item_table=it))
+        return torch.stack(cols, dim=1)
+
     def get_all_training_data(self):
-        u, i = self.pos_inter[:, 0].contiguous(), self.pos_inter[:, 1]
-        seed = (self._seed << 20) + self._epoch                          # a fresh stream every epoch
-        if self._n_cand == 1:
-            neg = self._pos.sample(u, seed, alias=self._alias)
-        else:
-            ut, it = self._score_tables()
-            neg = self._pos.sample(u, seed, n_cand=self._n_cand, alias=self._alias, user_table=ut, item_table=it)
+        neg = self.negatives(self._epoch)
         self._epoch += 1
-        data = torch.stack([u, i, neg], dim=1)
+        data = torch.cat([self.pos_inter[:, :2], neg], dim=1)
         perm = torch.randperm(data.shape[0], device=self.device, generator=self._gen)
         return data[perm].contiguous()
 
@@ -237,6 +249,7 @@ class DGCF_training_data(Abstract_training_data):
     def __init__(self, data, args=None, config=None, seed=None):
         super().__init__(args, config)
         cfg = config if config is not None else _GLOBAL_CFG
+        _lib.refuse_multi_negative(cfg, "DGCF_training_data")
         self.cor_batch = cfg.get("cor_batch", 100)
         self.use_tag = cfg["use_tag"]
         self.num_item, self.num_user, self.num_tag = data.num["item"], data.num["user"], data.num.get("tag", 0)

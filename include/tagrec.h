@@ -354,6 +354,39 @@ int tagrec_rank_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
                         int64_t B, int K, const float* coef, const float* g,
                         float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
 
+/* ---- In-batch sampled softmax on COMPACT rows: a fused B x B loss, the score matrix is never stored (csrc/inbatch.hip) ----
+ * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub, and every other row of Ib is
+ * a negative of it.  The kernels do not know what the two operands stand for (users / items, or two views of one node set).
+ * uid, iid: int64 [B], the ids behind the rows, read for the mask only (both NULL: nothing is masked).  col_bias: float [B]
+ * or NULL.  Ureg / Ireg [B, Dreg] (stride ldreg): the rows the L2 term reads (both NULL: no L2 term).
+ *   s_bj   = Ub[b] . Ib[j]                        (exact-fp32 MFMA 16x16x4, ascending feature blocks)
+ *   z_bj   = s_bj / temperature - col_bias[j]     (every j, the diagonal included)
+ *   masked   (b, j), j != b, with iid[j] == iid[b] (the row's own positive) or uid[j] == uid[b] (another positive of the same
+ *            user): left out of the softmax entirely
+ *   loss_b = logsumexp_{j unmasked} z_bj - z_bb   (running maximum; a row whose every other column is masked: exactly 0)
+ * fwd writes loss_out[0] = mean_b loss_b, loss_out[1] = 0.5 sum |row|^2 / B over the 2 B L2 rows (unweighted) and
+ * lse [B] = the row log-sum-exp the backward reads.  `partials`: scratch of 2*ceil(B/64) floats; the reduction over b runs
+ * in a fixed order.  D must be a multiple of 4 in 8 .. 256 and 1 <= B <= 65536, anything else is TAGREC_E_UNSUPPORTED. */
+int tagrec_inbatch_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                           const int64_t* uid, const int64_t* iid, const float* col_bias,
+                           const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                           int64_t B, float temperature,
+                           float* lse, float* partials, float* loss_out, void* stream);
+/* bwd STORES (no atomics, no read of the old contents; a pure function of its inputs, the summation order is a function of
+ * (B, D) only) every row of
+ *   dUb[b]     = sum_j C_bj Ib[j]                 (ascending j)
+ *   dIb[j]     = sum_b C_bj Ub[b]                 (ascending b)
+ *   C_bj       = g0 / (temperature B) * (exp(z_bj - lse[b]) - [b == j]), 0 where masked
+ *   dXreg[row] = g1 / B * Xreg[row]               for the 2 B L2 rows (dUreg = dIreg = NULL: not written)
+ * g = device pointer to two floats (upstream gradients of the two loss parts) or NULL for (1, 1).  dUreg = dUb and
+ * dIreg = dIb (one buffer for both parts) is allowed when Ureg = Ub, Ireg = Ib with the same stride and width: each row
+ * then receives the sum of its two terms in one store. */
+int tagrec_inbatch_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                           const int64_t* uid, const int64_t* iid, const float* col_bias,
+                           const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                           int64_t B, float temperature, const float* lse, const float* g,
+                           float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
+
 /* ---- N4: propagation with dynamic per-factor edge weights (DGCF model/dgcf.py:70-110, DisenGCN model/disengcn.py:23-46) --
  * The graph handle supplies the STRUCTURE (rowptr / colidx; its values are not read).  K factors own the column
  * slices [k D/K, (k+1) D/K) of an embedding row (torch.split / torch.cat along dim 1 in the reference).  Per-entry

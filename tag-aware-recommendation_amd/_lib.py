@@ -28,8 +28,13 @@ def refuse_deterministic(config, model, not_covered):
 
 
 def refuse_multi_negative(config, what):
-    """Models and producers that consume (user, positive, one negative) triplets refuse n_negatives != 1 and the "softmax"
-    loss loudly instead of training on the first negative (only the LightGCN and NGCF steps and BPR_training_data are covered)."""
+    """Models and producers that consume (user, positive, one negative) triplets refuse n_negatives != 1, the "softmax"
+    loss and negatives="in_batch" loudly instead of training on the first negative (only the LightGCN and NGCF steps and
+    BPR_training_data are covered)."""
+    neg = config.get("negatives", "sampled")
+    if neg != "sampled":
+        raise TagrecError(f"{what}: negatives={neg!r} is not covered (in-batch negatives: the LightGCN and NGCF steps and "
+                          "BPR_training_data only); it takes negatives=\"sampled\"")
     k, loss = config.get("n_negatives", 1), config.get("mul_loss_func")
     if k != 1 or loss == "softmax":
         raise TagrecError(f"{what}: n_negatives={k!r} / mul_loss_func={loss!r} is not covered (multi-negative losses: the "
@@ -74,6 +79,10 @@ _SIGNATURES = {
                             c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_rank_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_inbatch_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                               c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_inbatch_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                               c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_ngcf_wgrad_workspace": [c_int, c_int],
     "tagrec_ngcf_dense_fwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p],

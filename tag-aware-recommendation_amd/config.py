@@ -27,10 +27,14 @@ _BASE = {
     # multi-negative ranking losses (rowops.rank_fwd / rank_bwd; LightGCN, NGCF and BPR_training_data; the reference has K = 1)
     "n_negatives": 1,             # K negatives per positive: batches are [B, 2 + K]
     "loss_temperature": 1.0,      # tau of mul_loss_func = "softmax" (not read by the other kinds)
+    # where a positive's negatives come from (LightGCN, NGCF and BPR_training_data)
+    "negatives": "sampled",       # "in_batch": the other positives of the batch (rowops.inbatch_*); batches are [B, 2], nothing is sampled
+    "in_batch_logq": False,       # in-batch: subtract log(train degree of the item / train edges) from every column's logit
 }
 NEG_SAMPLING_MODES = ("uniform", "popularity")
 MAX_NEG_CANDIDATES = 16
 MUL_LOSS_FUNCS = ("softplus", "logsigmoid", "softmax")
+NEGATIVES_MODES = ("sampled", "in_batch")
 MAX_NEGATIVES = 63                # the kernel keeps the K + 1 scores of a tuple one per lane of a 64-lane wavefront
 
 # utility/config.py:1-12, 41-52
@@ -59,6 +63,7 @@ def get_config(model="lightgcn", **overrides):
     cfg.update(overrides)
     check_neg_sampling(cfg)
     check_ranking(cfg)
+    check_negatives(cfg)
     return cfg
 
 
@@ -86,6 +91,26 @@ def check_ranking(cfg):
     if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < float("inf"):
         raise TagrecError(f"loss_temperature must be a finite number > 0, got {tau!r}")
     return k, loss, float(tau)
+
+
+def check_negatives(cfg):
+    """The two in-batch keys of a config -> (in_batch, in_batch_logq); an unknown value, and negatives="in_batch" with anything
+    but mul_loss_func="softmax" and n_negatives=1 (in-batch and sampled negatives are not mixed), is refused."""
+    from ._lib import TagrecError
+    neg, logq = cfg.get("negatives", "sampled"), cfg.get("in_batch_logq", False)
+    if neg not in NEGATIVES_MODES:
+        raise TagrecError(f"unknown negatives {neg!r} (have {NEGATIVES_MODES})")
+    if not isinstance(logq, bool):
+        raise TagrecError(f"in_batch_logq must be True or False, got {logq!r}")
+    if neg == "in_batch":
+        k, loss = cfg.get("n_negatives", 1), cfg.get("mul_loss_func", "softplus")
+        if loss != "softmax":
+            raise TagrecError(f"negatives=\"in_batch\" is a softmax over the batch: it needs mul_loss_func=\"softmax\", got {loss!r}")
+        if k != 1:
+            raise TagrecError(f"negatives=\"in_batch\" samples nothing: it needs n_negatives=1, got {k!r}")
+    elif logq:
+        raise TagrecError("in_batch_logq=True corrects in-batch negatives: it needs negatives=\"in_batch\"")
+    return neg == "in_batch", logq
 
 
 CFG =get_config("lightgcn")

@@ -11,6 +11,8 @@ argument meaning, backed by the HIP library through `torch.autograd.Function`s.
 
 Inputs must be GPU tensors; there is no CPU path.
 """
+from typing import NamedTuple, Optional
+
 import torch
 
 from . import _lib, rowops
@@ -174,6 +176,122 @@ def ranking_loss(U, I, Ureg, Ireg, tuples, loss_func, temperature=1.0, plans=Non
     plans (`ranking_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
     instead of by `index_add_`."""
     out = _RankingLoss.apply(U, I, Ureg, Ireg, tuples, loss_kind_id(loss_func), float(temperature), plans)
+    return out[0], out[1]
+
+
+class _InBatchLoss(torch.autograd.Function):
+    """In-batch softmax loss on tables + a [B, 2] pair batch: the 2 B rows are gathered, the fused B x B kernels
+    (rowops.inbatch_fwd / inbatch_bwd) run on them and the compact gradients are folded back onto the tables.
+    Returns a 2-vector: [mul_loss, l2reg_loss (unweighted)]."""
+
+    @staticmethod
+    def forward(ctx, U, I, Ureg, Ireg, pairs, temperature, item_logq, plans):
+        for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2):
+                raise _lib.TagrecError(f"in_batch_loss: {nm} must be a 2-d float32 GPU tensor")
+        pairs = _lib.require_gpu_tensor(pairs.contiguous(), torch.int64, "in_batch_loss pairs")
+        if pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise _lib.TagrecError(f"in_batch_loss: pairs {tuple(pairs.shape)} must be [B, 2] = (user, positive)")
+        urows, irows = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+        bias = None if item_logq is None else item_logq.index_select(0, irows)
+        Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
+        has_reg = Ureg is not None
+        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
+        Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
+        out, lse = rowops.inbatch_fwd(Ub, Ib, Urb, Irb, temperature, urows, irows, bias)
+        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows, lse,
+                              bias if bias is not None else U.new_empty(0))
+        ctx.has_reg, ctx.same, ctx.plans, ctx.tau, ctx.has_bias = has_reg, same, plans, temperature, bias is not None
+        ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Ub, Ib, Urb, Irb, urows, irows, lse, bias = ctx.saved_tensors
+        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
+        dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
+        if ctx.has_reg and ctx.same:
+            Urb, Irb, dUrb, dIrb = Ub, Ib, dUb, dIb        # reg on the same rows: one gradient buffer
+        elif ctx.has_reg:
+            dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
+        else:
+            Urb = Irb = dUrb = dIrb = None
+        rowops.inbatch_bwd(Ub, Ib, Urb, Irb, ctx.tau, lse, g, dUb, dIb, dUrb, dIrb, urows, irows, bias if ctx.has_bias else None)
+
+        def fold(shape, rows, src, plan):
+            return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
+
+        dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
+        if ctx.has_reg and not ctx.same:
+            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
+        return dU, dI, None, None, None, None, None, None
+
+
+class InBatchRoute(NamedTuple):
+    """What a fused step is handed in place of `rank_route`'s (K, temperature) when the model has negatives="in_batch"."""
+    temperature: float
+    item_logq: Optional[torch.Tensor]      # [n_item] logQ table, or None: no column bias
+
+
+class InBatchState(NamedTuple):
+    """What the in-batch loss stage of a fused step keeps between its forward and its backward."""
+    temperature: float
+    uid: torch.Tensor                      # [B] the mask ids: the two columns of the pair batch
+    iid: torch.Tensor
+    bias: Optional[torch.Tensor]           # [B] item_logq of the batch's items, or None
+    lse: torch.Tensor                      # [B] row log-sum-exp written by the forward
+
+
+def in_batch_route(model, batch, temperature, item_logq=None):
+    """A model with negatives="in_batch" takes [B, 2] = (user, positive) batches; any other width is refused.
+    -> the `InBatchRoute` its step takes."""
+    if batch.dim() != 2 or batch.shape[1] != 2:
+        raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit negatives=\"in_batch\" "
+                               "(expected [B, 2] = user, positive; the negatives are the other positives of the batch)")
+    return InBatchRoute(float(temperature), item_logq)
+
+
+def in_batch_stage_fwd(route, pairs, Ub, Ib, Ureg, Ireg):
+    """The loss stage of a fused step on its gathered rows (users, then positives) -> (res, InBatchState)."""
+    uid, iid = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+    bias = None if route.item_logq is None else route.item_logq.index_select(0, iid)
+    res, lse = rowops.inbatch_fwd(Ub, Ib, Ureg, Ireg, route.temperature, uid, iid, bias)
+    return res, InBatchState(route.temperature, uid, iid, bias, lse)
+
+
+def in_batch_stage_bwd(state, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg):
+    """Its backward: one launch stores the gradient rows of both loss parts (`rowops.inbatch_bwd`)."""
+    rowops.inbatch_bwd(Ub, Ib, Ureg, Ireg, state.temperature, state.lse, g, dUb, dIb, dUreg, dIreg, state.uid, state.iid, state.bias)
+
+
+def in_batch_plans(pairs, n_user, n_item, width=256):
+    """(plan of the user rows, plan of the item rows) of a [B, 2] pair batch for `in_batch_loss(plans=...)`."""
+    return (rowops.row_list_plan(pairs[:, 0].contiguous(), n_user, None, width),
+            rowops.row_list_plan(pairs[:, 1].contiguous(), n_item, None, width))
+
+
+def item_logq_table(edge_index, n_item, device):
+    """log(train degree of the item / number of train edges) [n_item] float32, computed in float64: the logQ correction of
+    in-batch negatives (an item appears as an in-batch negative in proportion to its degree).  Degree 0 gives 0: such an
+    item never enters a batch."""
+    import numpy as np
+    edges = edge_index.cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)      # [E, 2] = (user, item)
+    items = edges[:, 1].astype(np.int64)
+    deg = np.bincount(items, minlength=n_item).astype(np.float64)
+    out = np.zeros(n_item, dtype=np.float64)
+    nz = deg > 0
+    out[nz] = np.log(deg[nz] / float(items.shape[0]))
+    return torch.from_numpy(out.astype(np.float32)).to(device)
+
+
+def in_batch_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, item_logq=None, plans=None):
+    """(mul_loss, l2reg_loss) of a [B, 2] batch (user, positive) with in-batch negatives: the other B - 1 positives of the
+    batch are every user's negatives, except the entries that name the same item or the same user (masked).
+    mul_loss = mean_b [logsumexp_{j unmasked}(z_bj) - z_bb], z_bj = u_b . i_j / temperature - item_logq[item_j] (None: no
+    correction); l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg (None: 0).  The B x B scores are never stored.
+    plans (`in_batch_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
+    instead of by `index_add_`."""
+    out = _InBatchLoss.apply(U, I, Ureg, Ireg, pairs, float(temperature), item_logq, plans)
     return out[0], out[1]
 
 

@@ -17,7 +17,7 @@ import torch
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
 from .graph import EdgeDropView, Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -257,7 +257,9 @@ class _PropagateBprLoss(torch.autograd.Function):
     def forward(ctx, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active, drops=None, seed=0, restrict=True,
                 fused_opt=None, ws=None, deterministic=False, rank=None):
         x0 = table.detach()
-        if rank is not None:          # (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*)
+        # rank = (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*);
+        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*)
+        if rank is not None:
             return _PropagateBprLoss._forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active,
                                                    drops, seed, restrict, fused_opt, ws, deterministic, rank)
         ctx.rank = None
@@ -294,8 +296,9 @@ class _PropagateBprLoss(torch.autograd.Function):
     @staticmethod
     def _forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, tuples, loss_kind, reg_active, drops, seed, restrict,
                       fused_opt, ws, deterministic, rank):
-        """The loss stage on `rowops.rank_fwd`: only the row list changes, T = (2 + K) B; everything around it is the triplet
-        step's.  The all-rows path gathers the T rows of `out` (the kernels take compact rows only)."""
+        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd`: only the row list changes, T = (2 + K) B (in-batch: K = 0);
+        everything around it is the triplet step's.  The all-rows path gathers the T rows of `out` (the kernels take compact
+        rows only)."""
         ctx.rank = rank
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         ctx.ws, ctx.token = None, _Token()
@@ -315,7 +318,11 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.drops, ctx.seed = drops, seed
             out_b = out.index_select(0, rows)
         ego_b = x0.index_select(0, rows)
-        res, ctx.coef = rowops.rank_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], loss_kind, rank[1])
+        ctx.in_batch = None
+        if isinstance(rank, H.InBatchRoute):
+            res, ctx.in_batch = H.in_batch_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
+        else:
+            res, ctx.coef = rowops.rank_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], loss_kind, rank[1])
         ctx.out_b, ctx.ego_b = out_b, ego_b
         return res
 
@@ -323,7 +330,14 @@ class _PropagateBprLoss(torch.autograd.Function):
     def _backward_rank(ctx, g):
         out_b, ego_b, rows, B = ctx.out_b, ctx.ego_b, ctx.rows, ctx.B
         d_b = torch.empty_like(out_b)                                      # d / d out_b: every row is stored by the kernel
-        rowops.rank_bwd(out_b[:B], out_b[B:], None, None, ctx.coef, g, d_b[:B], d_b[B:], None, None)
+        d_e = None
+        if ctx.in_batch is not None:  # one launch stores both parts (the L2 rows are folded after the hop, below)
+            d_e = torch.empty_like(ego_b) if ctx.reg_active else None
+            reg = (ego_b[:B], ego_b[B:], d_e[:B], d_e[B:]) if ctx.reg_active else (None,) * 4
+            H.in_batch_stage_bwd(ctx.in_batch, out_b[:B], out_b[B:], reg[0], reg[1], g, d_b[:B], d_b[B:], reg[2], reg[3])
+            ctx.in_batch = None
+        else:
+            rowops.rank_bwd(out_b[:B], out_b[B:], None, None, ctx.coef, g, d_b[:B], d_b[B:], None, None)
         if ctx.compact:
             fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
             g0 = restricted_backward(ctx.graph.transpose(), rows, d_b, ctx.state, ctx.shape, fused, ctx.ws, ctx.plan)
@@ -334,8 +348,9 @@ class _PropagateBprLoss(torch.autograd.Function):
             g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
             ctx.raws = ctx.invs = None
         if ctx.reg_active:                                                 # L2 term on the ego rows, after the hop has written g0
-            d_e = torch.empty_like(ego_b)
-            rowops.rank_bwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctx.coef, g, None, None, d_e[:B], d_e[B:], "rank_bwd(reg)")
+            if d_e is None:
+                d_e = torch.empty_like(ego_b)
+                rowops.rank_bwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctx.coef, g, None, None, d_e[:B], d_e[B:], "rank_bwd(reg)")
             rowops.fold_rows(g0, rows, d_e, ctx.plan)
         ctx.out_b = ctx.ego_b = None
         if ctx.ws is not None:
@@ -391,6 +406,8 @@ class LightGCN(FusedStepModel):
         self._init_table(data, self.use_tag, self.dim_latent, self.device)
         self.norm_adj = graph if graph is not None else creat_adj(data, self.use_tag, self.norm_type,
                                                                   self.split_adj_k, self.device)
+        # the logQ correction of in-batch negatives: log(train degree / train edges) per item, fixed at construction
+        self.item_logq = H.item_logq_table(data.edge_index["train"], self.num_list[1], self.device) if self.in_batch_logq else None
 
     def _config(self, config):
         self.dim_latent = config["dim_latent"]
@@ -401,6 +418,8 @@ class LightGCN(FusedStepModel):
         self.reg = config["reg"]
         # K negatives per positive: batches are [B, 2 + K]; K > 1 or "softmax" takes the multi-negative loss kernels
         self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
+        # negatives="in_batch": [B, 2] batches, the other positives of the batch are the negatives (rowops.inbatch_*)
+        self.in_batch, self.in_batch_logq = check_negatives(config)
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
         self.node_drop = config["node_drop"]
@@ -463,7 +482,10 @@ class LightGCN(FusedStepModel):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
-        rank = H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+        if self.in_batch:
+            rank = H.in_batch_route(type(self).__name__, batch_data, self.loss_temperature, self.item_logq)
+        else:
+            rank = H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         if self._fused_ok():
             graph = self._graph()                       # (first: kernel-mode edge dropout refuses a capture before any launch)
             drops, seed = self._drops()
@@ -477,6 +499,9 @@ class LightGCN(FusedStepModel):
             raise _lib.TagrecError("LightGCN: deterministic=True covers the fused step only (no row folds: split_adj_k == 1)")
         all_users, all_items = self.forward()[:2]
         ego = self.embed
+        if self.in_batch:
+            loss, reg_loss = H.in_batch_loss(all_users, all_items, ego[0], ego[1], batch_data, rank.temperature, rank.item_logq)
+            return loss, self.reg * reg_loss
         if rank is not None:
             loss, reg_loss = H.ranking_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func, rank[1])
             return loss, self.reg * reg_loss

@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
 from .graph import Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -341,7 +341,9 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.fused = (table, fused_opt) if fused_opt is not None else None
         wps = _wps([m.detach() for m in mats])
         ctx.rank = rank
-        if rank is not None:          # (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*)
+        # rank = (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*);
+        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*)
+        if rank is not None:
             return _PropagateBprLoss._forward_rank(ctx, graph, dims, n_user, trip, loss_kind, drops, seed, deterministic, x0, wps)
         B, n = trip.shape[0], x0.shape[0]
         rows = rowops.batch_rows(trip, n_user) if (RESTRICT_FORWARD or deterministic) else None
@@ -365,8 +367,9 @@ class _PropagateBprLoss(torch.autograd.Function):
 
     @staticmethod
     def _forward_rank(ctx, graph, dims, n_user, tuples, loss_kind, drops, seed, deterministic, x0, wps):
-        """The loss stage on `rowops.rank_fwd`: only the row list changes, T = (2 + K) B.  The all-rows path gathers the T rows
-        of `out` (the kernels take compact rows only); the L2 term reads the same propagated rows."""
+        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd`: only the row list changes, T = (2 + K) B (in-batch:
+        K = 0).  The all-rows path gathers the T rows of `out` (the kernels take compact rows only); the L2 term reads the same
+        propagated rows."""
         B, n = tuples.shape[0], x0.shape[0]
         rows = ctx.rows = rowops.tuple_rows(tuples, n_user)
         ctx.plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
@@ -379,7 +382,11 @@ class _PropagateBprLoss(torch.autograd.Function):
             out, ctx.saved = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
             out_b = out.index_select(0, rows)
         U, I = out_b[:B], out_b[B:]
-        res, ctx.coef = rowops.rank_fwd(U, I, U, I, loss_kind, ctx.rank[1])
+        ctx.in_batch = None
+        if isinstance(ctx.rank, H.InBatchRoute):
+            res, ctx.in_batch = H.in_batch_stage_fwd(ctx.rank, tuples, U, I, U, I)
+        else:
+            res, ctx.coef = rowops.rank_fwd(U, I, U, I, loss_kind, ctx.rank[1])
         ctx.out_b = out_b
         return res
 
@@ -388,7 +395,11 @@ class _PropagateBprLoss(torch.autograd.Function):
         out_b, B = ctx.out_b, ctx.B
         d_b = torch.empty_like(out_b)                   # both loss parts land in one buffer; every row is stored by the kernel
         U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
-        rowops.rank_bwd(U, I, U, I, ctx.coef, g, dU, dI, dU, dI)
+        if ctx.in_batch is not None:
+            H.in_batch_stage_bwd(ctx.in_batch, U, I, U, I, g, dU, dI, dU, dI)
+            ctx.in_batch = None
+        else:
+            rowops.rank_bwd(U, I, U, I, ctx.coef, g, dU, dI, dU, dI)
         if ctx.compact:
             d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
             ctx.state = None
@@ -442,6 +453,8 @@ class NGCF(FusedStepModel):
                 self.mat[name] = nn.Parameter(t.to(self.device))
         self.norm_adj = graph if graph is not None else creat_adj(data, self.use_tag, self.norm_type,
                                                                   self.split_adj_k, self.device)
+        # the logQ correction of in-batch negatives: log(train degree / train edges) per item, fixed at construction
+        self.item_logq = H.item_logq_table(data.edge_index["train"], self.num_list[1], self.device) if self.in_batch_logq else None
 
     def _config(self, config):
         self.dim_latent = config["dim_latent"]
@@ -455,6 +468,8 @@ class NGCF(FusedStepModel):
         self.reg = config["reg"]
         # K negatives per positive: batches are [B, 2 + K]; K > 1 or "softmax" takes the multi-negative loss kernels
         self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
+        # negatives="in_batch": [B, 2] batches, the other positives of the batch are the negatives (rowops.inbatch_*)
+        self.in_batch, self.in_batch_logq = check_negatives(config)
         self.use_tag = config["use_tag"]
         self.drop_seed = config.get("seed", 2020)
         # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
@@ -493,7 +508,10 @@ class NGCF(FusedStepModel):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
-        rank = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+        if self.in_batch:
+            rank = H.in_batch_route("NGCF", batch_data, self.loss_temperature, self.item_logq)
+        else:
+            rank = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         if self.agg_type == "bi_agg" and self._fused_ok():
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
@@ -505,6 +523,9 @@ class NGCF(FusedStepModel):
             raise _lib.TagrecError("NGCF: deterministic=True covers the fused step only (bi_agg, widths in {16, 32, 64, 128}, "
                                    "no row folds)")
         all_users, all_items = self.forward()[:2]
+        if self.in_batch:
+            loss, reg_loss = H.in_batch_loss(all_users, all_items, all_users, all_items, batch_data, rank.temperature, rank.item_logq)
+            return loss, self.reg * reg_loss
         if rank is not None:
             loss, reg_loss = H.ranking_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func, rank[1])
             return loss, self.reg * reg_loss

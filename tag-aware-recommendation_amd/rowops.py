@@ -186,6 +186,63 @@ def rank_bwd(Ub, Ib, Ureg, Ireg, coef, g, dUb, dIb, dUreg, dIreg, what="rank_bwd
                                      ptr(dUb), ptr(dIb), ptr(dUreg), ptr(dIreg), stream_ptr()), what)
 
 
+# ---- in-batch sampled softmax on compact rows: the fused B x B loss (csrc/inbatch.hip) ----
+
+INBATCH_TILE = 64        # rows per block of the in-batch kernels: `partials` holds two floats per block
+
+
+def _inbatch_args(what, Ub, Ib, Ureg, Ireg, uid, iid, col_bias):
+    """B of the operand pair Ub [B, D] / Ib [B, D] after the shape checks the two kernels share."""
+    if Ub is None or Ib is None or Ub.dim() != 2 or Ib.dim() != 2 or Ub.shape[0] != Ib.shape[0]:
+        raise _lib.TagrecError(f"{what}: Ub and Ib must be 2-d tensors with one row count (row b of Ib is the positive of row b of Ub)")
+    B = Ub.shape[0]
+    if B < 1:
+        raise _lib.TagrecError(f"{what}: an empty batch (B = 0) has no loss")
+    if (uid is None) != (iid is None):
+        raise _lib.TagrecError(f"{what}: uid / iid must both be given or both None")
+    for nm, t, dt in (("uid", uid, torch.int64), ("iid", iid, torch.int64), ("col_bias", col_bias, torch.float32)):
+        if t is not None and (t.dtype != dt or t.shape != (B,) or not t.is_contiguous() or t.device != Ub.device):
+            raise _lib.TagrecError(f"{what}: {nm} must be a contiguous {dt} tensor of shape [{B}] on {Ub.device}")
+    if Ureg is not None and Ireg is not None and (Ureg.shape[0] != B or Ireg.shape[0] != B):
+        raise _lib.TagrecError(f"{what}: Ureg {tuple(Ureg.shape)} / Ireg {tuple(Ireg.shape)} must have {B} rows")
+    return B
+
+
+def inbatch_fwd(Ub, Ib, Ureg, Ireg, temperature, uid=None, iid=None, col_bias=None):
+    """In-batch softmax loss of B (row, positive) pairs on gathered rows: every other row of Ib is a negative of row b of Ub,
+    except those whose iid equals iid[b] or whose uid equals uid[b] (masked).  Ureg / Ireg: the L2 rows (None: no L2 term).
+    -> (res = [mul_loss, l2reg_loss (unweighted)], lse [B] for `inbatch_bwd`).  The B x B scores are never stored."""
+    B = _inbatch_args("inbatch_fwd", Ub, Ib, Ureg, Ireg, uid, iid, col_bias)
+    ld, D = _pair_ld("inbatch_fwd", ("Ub", "Ib"), Ub, Ib)
+    ldreg, dreg = _pair_ld("inbatch_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
+    lse = torch.empty(B, dtype=torch.float32, device=Ub.device)
+    partials = torch.empty(2 * max(1, (B + INBATCH_TILE - 1) // INBATCH_TILE), dtype=torch.float32, device=Ub.device)
+    res = torch.empty(2, dtype=torch.float32, device=Ub.device)
+    check(load().tagrec_inbatch_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(uid), ptr(iid), ptr(col_bias), ptr(Ureg), ptr(Ireg), ldreg,
+                                        dreg, B, float(temperature), ptr(lse), ptr(partials), ptr(res), stream_ptr()),
+          "inbatch_fwd")
+    return res, lse
+
+
+def inbatch_bwd(Ub, Ib, Ureg, Ireg, temperature, lse, g, dUb, dIb, dUreg, dIreg, uid=None, iid=None, col_bias=None,
+                what="inbatch_bwd"):
+    """STORES the gradients of `inbatch_fwd`'s two loss parts (g = their upstream gradients, two floats; None: both 1) into
+    every row of dUb / dIb and dUreg / dIreg -- no atomics, the old contents are not read.  dUreg = dIreg = None: the L2
+    gradient is not written; dUreg is dUb and dIreg is dIb (with Ureg is Ub, Ireg is Ib): one buffer takes the sum."""
+    B = _inbatch_args(what, Ub, Ib, Ureg, Ireg, uid, iid, col_bias)
+    g = None if g is None else g.contiguous()
+    ld, D = _pair_ld(what, ("Ub", "Ib"), Ub, Ib, (dUb, dIb))
+    ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
+    if lse.shape != (B,) or not lse.is_contiguous() or lse.dtype != torch.float32:
+        raise _lib.TagrecError(f"{what}: lse {tuple(lse.shape)} must be a contiguous float32 [{B}] tensor")
+    for nm, t in (("dUb", dUb), ("dIb", dIb), ("dUreg", dUreg), ("dIreg", dIreg)):
+        if t is not None and t.shape[0] != B:
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {B} rows")
+    check(load().tagrec_inbatch_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(uid), ptr(iid), ptr(col_bias), ptr(Ureg), ptr(Ireg), ldreg,
+                                        dreg, B, float(temperature), ptr(lse), ptr(g), ptr(dUb), ptr(dIb), ptr(dUreg),
+                                        ptr(dIreg), stream_ptr()), what)
+
+
 def fold_rows(dst, rows, src, plan=None, accumulate=True):
     """dst[rows[j]] (+)= src[j]: through `plan` (the `row_list_plan` of rows) in a fixed order, else by `index_add_` (float
     atomics where the list names a row twice).  Without `accumulate` the listed rows of dst are overwritten with their sums."""

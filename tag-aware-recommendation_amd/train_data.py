@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import CFG as _GLOBAL_CFG, check_neg_sampling, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_neg_sampling, check_negatives, check_ranking
 
 
 def alias_table(weights):
@@ -164,7 +164,8 @@ def _sampler_keys(cfg, pos):
 
 class BPR_training_data(Abstract_training_data):
     """config["n_negatives"] = K negatives per train edge (default one: [E, 3] triplets; else [E, 2 + K] tuples), re-drawn
-    and shuffled every epoch.  With config["neg_candidates"] > 1 the epoch's
+    and shuffled every epoch; config["negatives"] = "in_batch": [E, 2] pairs, nothing is drawn, the shuffle is the same.
+    With config["neg_candidates"] > 1 the epoch's
     negatives are scored by `model` (given here or through `attach_model`): one eval-mode, no-grad `model.forward()` per
     epoch supplies the user and item tables `predict_rating` scores with."""
 
@@ -179,6 +180,8 @@ class BPR_training_data(Abstract_training_data):
         self._pos = _Positives(self.pos_inter[:, 0], self.pos_inter[:, 1], self.num_user, self.num)
         self._alias, self._n_cand = _sampler_keys(cfg, self._pos)
         self._n_neg = check_ranking(cfg)[0]          # K negatives per edge: the epoch array is [E, 2 + K]
+        # negatives="in_batch": the epoch array is [E, 2], the sampler is not launched (so no model is needed either)
+        self._in_batch = check_negatives(cfg)[0]
         self._model = model
         self._seed = int(cfg["seed"] if seed is None else seed)
         self._epoch = 0
@@ -186,7 +189,7 @@ class BPR_training_data(Abstract_training_data):
         self._gen.manual_seed(self._seed)
         self.tot_inter = self.pos_inter.shape[0] // self.batch_size
         # hard negatives need the model: without one the first epoch waits for attach_model() + reset()
-        if self._n_cand == 1 or model is not None:
+        if self._n_cand == 1 or model is not None or self._in_batch:
             self.all_train_data = self.get_all_training_data()
 
     def attach_model(self, model):
@@ -232,9 +235,11 @@ class BPR_training_data(Abstract_training_data):
         return torch.stack(cols, dim=1)
 
     def get_all_training_data(self):
-        neg = self.negatives(self._epoch)
+        if self._in_batch:                               # the shuffle draws from the same generator as the sampled producer
+            data = self.pos_inter[:, :2]
+        else:
+            data = torch.cat([self.pos_inter[:, :2], self.negatives(self._epoch)], dim=1)
         self._epoch += 1
-        data = torch.cat([self.pos_inter[:, :2], neg], dim=1)
         perm = torch.randperm(data.shape[0], device=self.device, generator=self._gen)
         return data[perm].contiguous()
 

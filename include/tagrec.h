@@ -220,6 +220,33 @@ int tagrec_spmm_axpy_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, 
 int tagrec_spmm_listed_edrop_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
                                  int D, float* ws, int64_t ws_floats, float ed_p, uint64_t ed_seed, int ed_transposed,
                                  void* stream);
+/* Noise perturbation of the SimGCL views (Yu et al., "Are Graph Augmentations Necessary?", SIGIR 2022) evaluated INSIDE the
+ * layer kernels: no noise tensor is stored, and the all-rows product, the row-masked product and the compact top layer
+ * perturb the same element the same way, because the direction is keyed by NODE ID, not by where the row is stored.
+ * For row r (node id), float4 index c (0 <= c < D / 4) of layer `layer` (1-based) of view `view` under the step's `seed`
+ *     key = mix64(seed ^ mix64((uint64(view) << 32) | uint32(layer)))            (mix64: the splitmix64 finaliser of the
+ *     h   = mix64(key ^ mix64((uint64(r) << 8) | uint64(c)))                       dropout masks)
+ *     u[4 c + j] = (((h >> 16 j) & 0xFFFF) + 1) * 2^-16,  j = 0 .. 3            (in (0, 1], exact in fp32)
+ *     n(r) = u / ||u||_2     (||u||^2: per float4 fma(u0,u0, fma(u1,u1, fma(u2,u2, u3 u3))), then an xor butterfly over c)
+ *     x'   = fma(eps sign(y), n(r), y),  sign(0) = 0       (an empty row stays zero; eps = 0: x' = y)
+ * D in {8, 16, 32, 64, 128, 256}; anything else is TAGREC_E_UNSUPPORTED.  eps finite and >= 0, view / layer >= 0.
+ *   spmm_norm_acc_noise : tagrec_spmm_norm_acc_rows_f32 (row_mask NULL = every row, rows outside the mask untouched, acc may
+ *                         be NULL) with y = the product row replaced by x' BEFORE the sum of squares: Y_raw holds x' (what the
+ *                         next layer gathers and what the unchanged backward kernels read), inv_norm = 1 / max(||x'||, 1e-12),
+ *                         acc += acc_scale x' inv_norm.  A long row is perturbed once, where its chunks are folded.
+ *   noise_rownorm_fwd   : rows of a COMPACT Y [n_rows, D] (e.g. from tagrec_spmm_listed_f32), row t being node node_ids[t]
+ *                         (NULL: node t): Y[t] <- x' in place, Z[t] = x' / max(||x'||, 1e-12) (row stride ldz),
+ *                         inv_norm[t] (may be NULL).  The same bits as spmm_norm_acc_noise gives for the same product row;
+ *                         with eps = 0 the bits of tagrec_rownorm_fwd_f32.
+ *   noise_dir           : out[t] = n(node_ids[t]) (NULL: n(t)), [n_rows, D] -- for tests and microbenchmarks; no training
+ *                         step calls it. */
+int tagrec_spmm_norm_acc_noise_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm, float* acc,
+                                   float acc_scale, const uint8_t* row_mask, float eps, uint64_t seed, int view, int layer,
+                                   int D, void* stream);
+int tagrec_noise_rownorm_fwd_f32(float* Y, const int64_t* node_ids, int64_t n_rows, float eps, uint64_t seed, int view,
+                                 int layer, float* Z, int64_t ldz, float* inv_norm, int D, void* stream);
+int tagrec_noise_dir_f32(float* out, const int64_t* node_ids, int64_t n_rows, uint64_t seed, int view, int layer, int D,
+                         void* stream);
 /* The masked hop below the top layer of a restricted step, driven by an inverted list of the batch rows' entries instead
  * of a walk over every masked row: G_out[j] = sum_b A[j, b] G_in[b] over the listed rows b, for the rows j of row_mask.
  *   batch_hop_plan   : gt = the TRANSPOSE of A (A itself when A is symmetric); rows = the n_listed (<= 16384) batch rows,

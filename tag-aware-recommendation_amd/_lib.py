@@ -176,6 +176,12 @@ _SIGNATURES = {
                                           c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
     "tagrec_spmm_listed_edrop_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float,
                                      ctypes.c_uint64, c_int, c_void_p],
+    # noise perturbation of the SimGCL views inside the layer kernels: (eps, seed, view, layer) key the direction by node id
+    "tagrec_spmm_norm_acc_noise_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float,
+                                       ctypes.c_uint64, c_int, c_int, c_int, c_void_p],
+    "tagrec_noise_rownorm_fwd_f32": [c_void_p, c_void_p, c_int64, c_float, ctypes.c_uint64, c_int, c_int, c_void_p, c_int64,
+                                     c_void_p, c_int, c_void_p],
+    "tagrec_noise_dir_f32": [c_void_p, c_void_p, c_int64, ctypes.c_uint64, c_int, c_int, c_int, c_void_p],
     "tagrec_batch_hop_workspace": [c_int64, c_int64, c_int64],
     "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

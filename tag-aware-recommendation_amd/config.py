@@ -50,6 +50,10 @@ _PER_MODEL = {
                  "cor_loss": False},
     # utility/config.py:54-61 -- note the default agg_type "bi_agg" switches KGAT's propagation off (kgat.py:100)
     "kgat": {"dim_relation": 64, "transe_reg": 0.0001, "transe_batch": 1024, "agg_type": "bi_agg", "mul_loss_func": "softplus"},
+    # SimGCL (not in the reference): LightGCN plus an InfoNCE term between two noise-perturbed views of the batch's nodes
+    # (simgcl.py); cl_rate weighs the term, cl_eps is the length of the per-layer perturbation, cl_temperature its tau
+    "simgcl": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100,
+               "cl_rate": 0.5, "cl_eps": 0.1, "cl_temperature": 0.2, "use_tag": False},
 }
 
 
@@ -64,6 +68,8 @@ def get_config(model="lightgcn", **overrides):
     check_neg_sampling(cfg)
     check_ranking(cfg)
     check_negatives(cfg)
+    if model == "simgcl":
+        check_contrastive(cfg)
     return cfg
 
 
@@ -111,6 +117,18 @@ def check_negatives(cfg):
     elif logq:
         raise TagrecError("in_batch_logq=True corrects in-batch negatives: it needs negatives=\"in_batch\"")
     return neg == "in_batch", logq
+
+
+def check_contrastive(cfg):
+    """The three contrastive keys of a SimGCL config -> (cl_rate, cl_eps, cl_temperature); a bad value is refused."""
+    from ._lib import TagrecError
+    rate, eps, tau = cfg.get("cl_rate", 0.5), cfg.get("cl_eps", 0.1), cfg.get("cl_temperature", 0.2)
+    for name, v in (("cl_rate", rate), ("cl_eps", eps)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf"):
+            raise TagrecError(f"{name} must be a finite number >= 0, got {v!r}")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < float("inf"):
+        raise TagrecError(f"cl_temperature must be a finite number > 0, got {tau!r}")
+    return float(rate), float(eps), float(tau)
 
 
 CFG =get_config("lightgcn")

@@ -77,6 +77,35 @@ __host__ __device__ inline bool edge_kept(const EdgeDrop& d, int64_t row, int co
   return (h >> 40) >= static_cast<unsigned>(d.p * 16777216.0f);     // keep iff the 24-bit draw >= p * 2^24
 }
 
+// Noise direction of the SimGCL views (Yu et al., SIGIR 2022; include/tagrec.h has the key formula): the random unit vector
+// that perturbs row `node` of a layer's product is a pure function of (step seed, view, layer, NODE ID, float4 index within
+// the row), so the all-rows product, the row-masked one and the compact top layer perturb the same element the same way and
+// nothing is stored.  One hash per float4: four 16-bit fields -> u in (0, 1], exact in fp32.  Every kernel that applies the
+// perturbation sums ||u||^2 in ONE order (noise_ss4 per float4, then an xor butterfly over the row's float4 indices) and
+// goes through noise_apply, so that they give the same bits.
+struct NoiseDir {
+  float eps;        // length of the perturbation; 0 = the row passes unchanged
+  uint64_t key;     // noise_key(seed, view, layer)
+};
+__host__ __device__ inline uint64_t noise_key(uint64_t seed, int view, int layer) {
+  return mix64(seed ^ mix64((static_cast<uint64_t>(static_cast<uint32_t>(view)) << 32) | static_cast<uint32_t>(layer)));
+}
+__device__ __forceinline__ void noise_u4(uint64_t key, int64_t node, int c4, float& a, float& b, float& c, float& d) {
+  const uint64_t h = mix64(key ^ mix64((static_cast<uint64_t>(node) << 8) | static_cast<uint64_t>(c4)));
+  a = static_cast<float>(((h >> 0) & 0xFFFFu) + 1u) * (1.0f / 65536.0f);
+  b = static_cast<float>(((h >> 16) & 0xFFFFu) + 1u) * (1.0f / 65536.0f);
+  c = static_cast<float>(((h >> 32) & 0xFFFFu) + 1u) * (1.0f / 65536.0f);
+  d = static_cast<float>(((h >> 48) & 0xFFFFu) + 1u) * (1.0f / 65536.0f);
+}
+__device__ __forceinline__ float noise_ss4(float a, float b, float c, float d) {
+  return fmaf(a, a, fmaf(b, b, fmaf(c, c, d * d)));
+}
+// y + eps sign(y) u / ||u||, sign(0) = 0 (an empty row stays zero); eps = 0 returns y
+__device__ __forceinline__ float noise_apply(float y, float u, float u_norm, float eps) {
+  const float se = y > 0.f ? eps : (y < 0.f ? -eps : 0.f);
+  return fmaf(se, u / u_norm, y);
+}
+
 // torch.optim.Adam's update (_single_tensor_adam: exp_avg.lerp_(grad, 1 - b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad,
 // 1 - b2); param.addcdiv_(exp_avg, sqrt(exp_avg_sq) / sqrt(bc2) + eps, -step_size)), shared by the Adam kernels (rowops.hip)
 // and the last backward hop's fused epilogue (spmm.hip).  The roundings are PINNED -- contraction off, the three fused

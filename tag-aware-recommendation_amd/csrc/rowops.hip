@@ -37,6 +37,71 @@ __global__ __launch_bounds__(kThreads) void rownorm_fwd_kernel(const float* __re
   if (lane == 0 && inv_norm) inv_norm[r] = 1.0f / den;
 }
 
+// K19, the compact top layer of a SimGCL view: row t of Y (the product at node node_ids[t], from spmm_listed) is perturbed in
+// place by the noise direction of that NODE (NoiseDir, common.h) and normalised in the same pass.  D = 4 LPR.  The lanes
+// stride the columns exactly as in rownorm_fwd_kernel, so with eps = 0 this kernel gives rownorm_fwd's bits; ||u||^2 is
+// summed in the order of the product epilogue (csrc/spmm.hip: noise_ss4 per float4, then an xor butterfly over the float4
+// indices -- here 4 m lanes apart, and across the lane's own registers from float4 index 16 up), so the perturbed row has
+// the bits the all-rows kernel gives for the same product row.
+template <int LPR>
+__global__ __launch_bounds__(kThreads) void noise_rownorm_fwd_kernel(float* __restrict__ Y, const int64_t* __restrict__ node_ids,
+                                                                     NoiseDir nd, float* __restrict__ Z, int64_t ldz,
+                                                                     float* __restrict__ inv_norm, int64_t n_rows) {
+  constexpr int D = 4 * LPR;
+  constexpr int NJ = (D + kWave - 1) / kWave;        // elements per lane: k = lane + 64 j
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + (threadIdx.x >> 6);
+  if (t >= n_rows) return;                           // (a whole wavefront leaves)
+  const int64_t node = node_ids ? node_ids[t] : t;
+  float* y = Y + t * D;
+  float x[NJ], u[NJ], p[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int k = lane + kWave * j;
+    const bool active = k < D;
+    float u4[4];
+    noise_u4(nd.key, node, k >> 2, u4[0], u4[1], u4[2], u4[3]);
+    p[j] = active ? noise_ss4(u4[0], u4[1], u4[2], u4[3]) : 0.f;
+    const int f = k & 3;
+    u[j] = f == 0 ? u4[0] : (f == 1 ? u4[1] : (f == 2 ? u4[2] : u4[3]));
+    x[j] = active ? y[k] : 0.f;
+  }
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) {                // group_sum<LPR> over float4 index i = lane / 4 + 16 j
+    if (4 * m < kWave) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) p[j] += __shfl_xor(p[j], 4 * m);
+    } else {
+      float q[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) q[j] = p[j ^ ((4 * m) / kWave)];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) p[j] += q[j];
+    }
+  }
+  const float un = sqrtf(p[0]);
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (lane + kWave * j < D) {
+      x[j] = noise_apply(x[j], u[j], un, nd.eps);
+      ss = fmaf(x[j], x[j], ss);
+    }
+  }
+  ss = wave_sum(ss);
+  const float den = fmaxf(sqrtf(ss), 1e-12f);
+  float* z = Z + t * ldz;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int k = lane + kWave * j;
+    if (k < D) {
+      y[k] = x[j];
+      z[k] = x[j] / den;
+    }
+  }
+  if (lane == 0 && inv_norm) inv_norm[t] = 1.0f / den;
+}
+
 __global__ __launch_bounds__(kThreads) void rownorm_bwd_kernel(const float* __restrict__ Xraw,
                                                                const float* __restrict__ inv_norm,
                                                                const float* __restrict__ dZ, int64_t lddz, float s,
@@ -652,6 +717,31 @@ extern "C" int tagrec_rownorm_fwd_f32(const float* X, float* Z, int64_t ldz, flo
   if (n_rows == 0) return TAGREC_OK;
   const unsigned blocks = static_cast<unsigned>((n_rows + 3) / 4);
   rownorm_fwd_kernel<<<blocks, kThreads, 0, static_cast<hipStream_t>(stream)>>>(X, Z, ldz, inv_norm, n_rows, D);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_noise_rownorm_fwd_f32(float* Y, const int64_t* node_ids, int64_t n_rows, float eps, uint64_t seed, int view,
+                                            int layer, float* Z, int64_t ldz, float* inv_norm, int D, void* stream) {
+  TAGREC_REQUIRE(n_rows >= 0 && (n_rows == 0 || (Y && Z)), "noise_rownorm_fwd: null pointer or negative row count");
+  TAGREC_REQUIRE(n_rows == 0 || Y != Z, "noise_rownorm_fwd: Z aliases Y (Y keeps the perturbed raw rows)");
+  TAGREC_REQUIRE(eps >= 0.f && eps < INFINITY, "noise_rownorm_fwd: eps must be finite and >= 0");
+  TAGREC_REQUIRE(view >= 0 && layer >= 0, "noise_rownorm_fwd: view and layer must be >= 0");
+  if (!(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256))
+    return fail(TAGREC_E_UNSUPPORTED, "noise_rownorm_fwd: D must be 8 .. 256, a power of two");
+  TAGREC_REQUIRE(ldz >= D, "noise_rownorm_fwd: bad shape");
+  if (n_rows == 0) return TAGREC_OK;
+  const NoiseDir nd{eps, noise_key(seed, view, layer)};
+  const unsigned blocks = static_cast<unsigned>((n_rows + 3) / 4);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (D) {
+    case 8: noise_rownorm_fwd_kernel<2><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+    case 16: noise_rownorm_fwd_kernel<4><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+    case 32: noise_rownorm_fwd_kernel<8><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+    case 64: noise_rownorm_fwd_kernel<16><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+    case 128: noise_rownorm_fwd_kernel<32><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+    default: noise_rownorm_fwd_kernel<64><<<blocks, kThreads, 0, s>>>(Y, node_ids, nd, Z, ldz, inv_norm, n_rows); break;
+  }
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }

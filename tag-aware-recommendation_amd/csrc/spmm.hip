@@ -551,6 +551,115 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_finish_kernel(Gra
   row_epilogue<LPR, EPI>(acc, r, lane, e);
 }
 
+// ---- K19: the perturbed layer of a SimGCL view: NORM_ACC with the noise direction added to the product row first ----------
+// x' = y + eps sign(y) n(r), n(r) = u / ||u|| drawn from (key, NODE ID r, float4 index) (NoiseDir, common.h); x' is what is
+// stored, normalised and accumulated, and what the next layer gathers.  The hash sits in the epilogue, after the gather has
+// retired its registers: one mix64 pair per lane and one extra group_sum for ||u||^2.  Kernels of their own, so that the
+// plain products keep their names, code and register allocation (the precedent: the `_edrop` forms).  A long row is
+// perturbed where its chunks are folded (spmm_finish_noise_kernel), never per chunk.
+template <int LPR>
+__device__ __forceinline__ void row_epilogue_noise(float4 acc, int64_t r, int lane, const EpiArgs& e, const NoiseDir& nd) {
+  const bool writer = lane < LPR;
+  const int c4 = lane % LPR;
+  const int64_t off = r * LPR + c4;
+  float4 u;
+  noise_u4(nd.key, r, c4, u.x, u.y, u.z, u.w);
+  const float un = sqrtf(group_sum<LPR>(noise_ss4(u.x, u.y, u.z, u.w)));
+  acc.x = noise_apply(acc.x, u.x, un, nd.eps);
+  acc.y = noise_apply(acc.y, u.y, un, nd.eps);
+  acc.z = noise_apply(acc.z, u.z, un, nd.eps);
+  acc.w = noise_apply(acc.w, u.w, un, nd.eps);
+  const float ss = group_sum<LPR>(f4_dot(acc, acc));       // from here on: the EPI_NORM_ACC epilogue of row_epilogue
+  const float den = fmaxf(sqrtf(ss), 1e-12f);
+  if (writer) {
+    st_stream(reinterpret_cast<float4*>(e.Y) + off, acc);
+    if (e.accum) {
+      float4 a = ld_stream(reinterpret_cast<const float4*>(e.accum) + off);
+      a.x = fmaf(e.s, acc.x / den, a.x);
+      a.y = fmaf(e.s, acc.y / den, a.y);
+      a.z = fmaf(e.s, acc.z / den, a.z);
+      a.w = fmaf(e.s, acc.w / den, a.w);
+      st_stream(reinterpret_cast<float4*>(e.accum) + off, a);
+    }
+  }
+  if (lane == 0) e.inv_norm[r] = 1.0f / den;
+}
+
+template <int LPR, bool MASKED = false>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_noise_kernel(GraphView g, const float* __restrict__ X,
+                                                                                  EpiArgs e, LongView lv, NoiseDir nd) {
+  const int lane = threadIdx.x & (kWave - 1);
+  if (blockIdx.x < lv.chunk_blocks) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    if (c >= lv.n_chunks) return;
+    const int2 d = lv.chunk_desc[c];
+    if (d.x < 0) return;                    // unused slot of a handle created without a host read
+    const int64_t r = lv.long_rows[d.x];
+    if (MASKED && !e.row_mask[r]) return;
+    const int64_t start = g.rowptr[r] + static_cast<int64_t>(d.y) * kChunk;
+    const int64_t row_end = g.rowptr[r + 1];
+    const int64_t end = (start + kChunk < row_end) ? start + kChunk : row_end;
+    const float4 acc = gather_rows<LPR>(g, X, start, end, lane);
+    if (lane < LPR) reinterpret_cast<float4*>(lv.slab)[c * LPR + lane] = acc;
+    return;
+  }
+  const int64_t r = static_cast<int64_t>(blockIdx.x - lv.chunk_blocks) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (r >= g.n_rows) return;
+  if (MASKED && !e.row_mask[r]) return;
+  const int64_t start = g.rowptr[r], end = g.rowptr[r + 1];
+  if (end - start > kLongRow) return;  // chunked above, folded by spmm_finish_noise_kernel
+  const float4 acc = gather_rows<LPR>(g, X, start, end, lane);
+  row_epilogue_noise<LPR>(acc, r, lane, e, nd);
+}
+
+// the fold of spmm_finish_kernel (same chunk order: the same product bits), then the noise epilogue on the whole row
+template <int LPR, bool MASKED = false>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_finish_noise_kernel(GraphView g,
+                                                                                    const int32_t* __restrict__ long_rows,
+                                                                                    const int32_t* __restrict__ long_base,
+                                                                                    int64_t n_long, const float* __restrict__ slab,
+                                                                                    EpiArgs e, NoiseDir nd) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t li = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+  if (li >= n_long) return;
+  const int64_t r = long_rows[li];
+  if (r < 0) return;                        // unused slot of a handle created without a host read
+  if (MASKED && !e.row_mask[r]) return;
+  const int64_t deg = g.rowptr[r + 1] - g.rowptr[r];
+  const int nc = static_cast<int>((deg + kChunk - 1) / kChunk);
+  const float4* p = reinterpret_cast<const float4*>(slab) + static_cast<int64_t>(long_base[li]) * LPR + (lane % LPR);
+  constexpr int NPI = kWave / LPR;
+  auto add = [](float4& a, const float4& x) { a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w; };
+  float4 acc = f4_zero();
+  int k = lane / LPR;
+  for (; k + 3 * NPI < nc; k += 4 * NPI) {
+    const float4 x0 = p[static_cast<int64_t>(k) * LPR], x1 = p[static_cast<int64_t>(k + NPI) * LPR];
+    const float4 x2 = p[static_cast<int64_t>(k + 2 * NPI) * LPR], x3 = p[static_cast<int64_t>(k + 3 * NPI) * LPR];
+    add(acc, x0); add(acc, x1); add(acc, x2); add(acc, x3);
+  }
+  for (; k < nc; k += NPI) add(acc, p[static_cast<int64_t>(k) * LPR]);
+#pragma unroll
+  for (int m = LPR; m < kWave; m <<= 1) add(acc, f4_shfl_xor(acc, m));
+  row_epilogue_noise<LPR>(acc, r, lane, e, nd);
+}
+
+// n(r) itself, one lane group of LPR lanes per row (64 / LPR rows per wavefront): what the two kernels above and
+// noise_rownorm_fwd_kernel (rowops.hip) evaluate on the fly, for tests and the microbenchmark
+template <int LPR>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) void noise_dir_kernel(float* __restrict__ out, const int64_t* __restrict__ node_ids,
+                                                                            int64_t n_rows, uint64_t key) {
+  constexpr int NPI = kWave / LPR;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int c4 = lane % LPR;
+  const int64_t t = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6)) * NPI + lane / LPR;
+  const bool ok = t < n_rows;
+  const int64_t node = ok ? (node_ids ? node_ids[t] : t) : 0;
+  float4 u;
+  noise_u4(key, node, c4, u.x, u.y, u.z, u.w);
+  const float un = sqrtf(group_sum<LPR>(noise_ss4(u.x, u.y, u.z, u.w)));
+  if (ok) reinterpret_cast<float4*>(out)[t * LPR + c4] = make_float4(u.x / un, u.y / un, u.z / un, u.w / un);
+}
+
 // ---- any width D <= 512: scalar columns, one neighbour row per instruction ---------------------
 template <int EPI>
 __global__ __launch_bounds__(kWavesPerBlock * kWave) void spmm_rows_generic_kernel(GraphView g, const float* __restrict__ X,
@@ -1642,6 +1751,90 @@ extern "C" int tagrec_spmm_ss_rows_f32(const tagrec_graph* g, const float* X, fl
   TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_ss_rows: D must be 8 .. 256, a power of two");
   EpiArgs e{Y, ss, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask};
   return launch_spmm<EPI_SS>(g, X, e, D, stream, "spmm_ss_rows");
+}
+
+// ---- K19: the perturbed layers of the SimGCL views (NoiseDir in common.h; the key formula is in include/tagrec.h) ----------
+namespace {
+int noise_args(const char* who, float eps, int view, int layer, int D) {
+  TAGREC_REQUIRE(eps >= 0.f && eps < INFINITY, std::string(who) + ": eps must be finite and >= 0");
+  TAGREC_REQUIRE(view >= 0 && layer >= 0, std::string(who) + ": view and layer must be >= 0");
+  if (!(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256))
+    return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": the noise forms need a vector-kernel width (D must be 8 .. 256, a power of two)");
+  return TAGREC_OK;
+}
+
+template <int LPR>
+int launch_vec_noise(const tagrec_graph* g, const float* X, const EpiArgs& e, const NoiseDir& nd, hipStream_t s) {
+  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
+  const int threads = kWavesPerBlock * kWave;
+  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
+  LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
+  if (g->n_long > 0) {
+    int rc = ensure_slab(g, LPR * 4);
+    if (rc != TAGREC_OK) return rc;
+    lv.slab = g->slab;
+    lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
+  }
+  if (e.row_mask) spmm_rows_noise_kernel<LPR, true><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, nd);
+  else spmm_rows_noise_kernel<LPR><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, nd);
+  TAGREC_LAUNCH_CHECK();
+  if (g->n_long > 0) {
+    const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (e.row_mask) spmm_finish_noise_kernel<LPR, true><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
+    else spmm_finish_noise_kernel<LPR><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
+    TAGREC_LAUNCH_CHECK();
+  }
+  return TAGREC_OK;
+}
+}  // namespace
+
+extern "C" int tagrec_spmm_norm_acc_noise_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm, float* acc,
+                                              float acc_scale, const uint8_t* row_mask, float eps, uint64_t seed, int view,
+                                              int layer, int D, void* stream) {
+  TAGREC_REQUIRE(g != nullptr && X != nullptr && Y_raw != nullptr && inv_norm != nullptr, "spmm_norm_acc_noise: null pointer");
+  TAGREC_REQUIRE(static_cast<const void*>(X) != static_cast<const void*>(Y_raw), "spmm_norm_acc_noise: output aliases the gathered input");
+  int rc = noise_args("spmm_norm_acc_noise", eps, view, layer, D);
+  if (rc != TAGREC_OK) return rc;
+  if (!(aligned16(X) && aligned16(Y_raw) && (!acc || aligned16(acc))))
+    return fail(TAGREC_E_UNSUPPORTED, "spmm_norm_acc_noise: the vector kernels need 16-byte aligned rows");
+  if (g->n_rows == 0) return TAGREC_OK;
+  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask, nullptr};
+  const NoiseDir nd{eps, noise_key(seed, view, layer)};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (D) {
+    case 8: return launch_vec_noise<2>(g, X, e, nd, s);
+    case 16: return launch_vec_noise<4>(g, X, e, nd, s);
+    case 32: return launch_vec_noise<8>(g, X, e, nd, s);
+    case 64: return launch_vec_noise<16>(g, X, e, nd, s);
+    case 128: return launch_vec_noise<32>(g, X, e, nd, s);
+    default: return launch_vec_noise<64>(g, X, e, nd, s);
+  }
+}
+
+extern "C" int tagrec_noise_dir_f32(float* out, const int64_t* node_ids, int64_t n_rows, uint64_t seed, int view, int layer, int D,
+                                    void* stream) {
+  TAGREC_REQUIRE(n_rows >= 0 && (n_rows == 0 || out != nullptr), "noise_dir: null output or negative row count");
+  int rc = noise_args("noise_dir", 0.f, view, layer, D);
+  if (rc != TAGREC_OK) return rc;
+  TAGREC_REQUIRE(aligned16(out), "noise_dir: out must be 16-byte aligned");
+  if (n_rows == 0) return TAGREC_OK;
+  const uint64_t key = noise_key(seed, view, layer);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define NOISE_DIR(L)                                                                                              \
+  noise_dir_kernel<L><<<static_cast<unsigned>((n_rows + kWavesPerBlock * (kWave / L) - 1) / (kWavesPerBlock * (kWave / L))), \
+                        kWavesPerBlock * kWave, 0, s>>>(out, node_ids, n_rows, key);                              \
+  break
+  switch (D) {
+    case 8: NOISE_DIR(2);
+    case 16: NOISE_DIR(4);
+    case 32: NOISE_DIR(8);
+    case 64: NOISE_DIR(16);
+    case 128: NOISE_DIR(32);
+    default: NOISE_DIR(64);
+  }
+#undef NOISE_DIR
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
 }
 
 // ---- edge dropout inside the products (`node_drop`, /root/reference/model/help/adj.py:170-191; EdgeDrop in common.h) -------

@@ -427,6 +427,18 @@ class Graph:
                    _lib.ptr(inv_norm), _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), D,
                    _lib.stream_ptr())
 
+    def spmm_norm_acc_noise(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, eps, seed, view, layer):
+        """`spmm_norm_acc_rows` with the SimGCL perturbation in the epilogue: row r of the product becomes
+        y + eps sign(y) n(r) before it is stored, normalised and accumulated; n(r) is the unit direction drawn from
+        (seed, view, layer, node id r) -- include/tagrec.h has the key.  D in VEC_WIDTHS."""
+        D = self._chk_x(X, self.shape[1], "spmm_norm_acc_noise X")
+        self._chk_dev(X, "spmm_norm_acc_noise X")
+        self._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
+        self._call("spmm_norm_acc_noise_rows" if row_mask is not None else "spmm_norm_acc_noise",
+                   _lib.load().tagrec_spmm_norm_acc_noise_f32, self._h, _lib.ptr(X), _lib.ptr(y_raw), _lib.ptr(inv_norm),
+                   _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(eps), int(seed), int(view), int(layer), D,
+                   _lib.stream_ptr())
+
     def _chk_norm_acc_rows(self, D, y_raw, inv_norm, acc, row_mask):
         self._chk_w(y_raw, self.shape[0], D, "spmm_norm_acc_rows y_raw")
         self._chk_vec(inv_norm, self.shape[0], torch.float32, "spmm_norm_acc_rows inv_norm")

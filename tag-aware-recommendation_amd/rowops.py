@@ -23,6 +23,42 @@ def rownorm_fwd(x, z=None, inv=None):
     return z, inv
 
 
+def _node_ids(what, node_ids, T, device):
+    if node_ids is not None and (node_ids.dtype != torch.int64 or node_ids.shape != (T,) or not node_ids.is_contiguous()
+                                 or node_ids.device != device):
+        raise _lib.TagrecError(f"{what}: node_ids must be a contiguous int64 tensor of shape [{T}] on {device}")
+
+
+def noise_rownorm_fwd(y, node_ids, eps, seed, view, layer, z=None, inv=None):
+    """The compact top layer of a SimGCL view: row t of y (the product at node node_ids[t]; None: node t) is perturbed IN
+    PLACE, y + eps sign(y) n(node), and normalised in the same pass -> (z, inv).  n: `noise_dir`.  D in VEC_WIDTHS."""
+    _lib.require_gpu_tensor(y, torch.float32, "noise_rownorm_fwd: y")
+    T, D = y.shape
+    _node_ids("noise_rownorm_fwd", node_ids, T, y.device)
+    if z is None:
+        z = torch.empty(T, D, dtype=torch.float32, device=y.device)
+    if inv is None:
+        inv = torch.empty(T, dtype=torch.float32, device=y.device)
+    check(load().tagrec_noise_rownorm_fwd_f32(ptr(y), ptr(node_ids), T, float(eps), int(seed), int(view), int(layer), ptr(z),
+                                              z.stride(0) if T > 1 else D, ptr(inv), D, stream_ptr()), "noise_rownorm_fwd")
+    return z, inv
+
+
+def noise_dir(node_ids, D, seed, view, layer, device=None):
+    """n(r) [T, D] of the SimGCL perturbation for the nodes `node_ids` (int64 [T]; an int T: nodes 0 .. T - 1): the unit
+    direction the layer kernels draw on the fly from (seed, view, layer, node id) -- for tests and microbenchmarks."""
+    if isinstance(node_ids, int):
+        T, ids = node_ids, None
+        if device is None:
+            raise _lib.TagrecError("noise_dir: a row count needs a device")
+    else:
+        T, ids, device = node_ids.numel(), node_ids, node_ids.device
+        _node_ids("noise_dir", ids, T, device)
+    out = torch.empty(T, D, dtype=torch.float32, device=device)
+    check(load().tagrec_noise_dir_f32(ptr(out), ptr(ids), T, int(seed), int(view), int(layer), D, stream_ptr()), "noise_dir")
+    return out
+
+
 def rownorm_bwd(x_raw, inv, dz, s, out, accumulate=False):
     """out (+)= normalize-backward(x_raw, inv, s * dz); dz may be a strided slot view."""
     n, D = x_raw.shape

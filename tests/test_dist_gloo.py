@@ -4,6 +4,7 @@ The local kernels are replaced by a CPU test double built from torch ops (`CpuOp
 checks the partitioning, the all-gather / all-reduce plumbing, the batch-row exchange and the
 gradient scatter of tagrec_amd/dist.py against the single-process oracle.  The HIP kernels
 themselves are checked in the -m gpu tests."""
+import gc
 import os
 
 import numpy as np
@@ -317,7 +318,8 @@ def _worker(rank, world, init, out_dir, n_layer, n_chunks, restrict, all_gather=
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(1)
     dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
-    try:
+
+    def run():
         fx = load_golden("lightgcn_toy")
         m, csr, full = _row_model(rank, world, fx, n_layer, n_chunks, restrict, all_gather=all_gather)
         opt = torch.optim.Adam(m.parameters(), lr=0.01)
@@ -335,6 +337,14 @@ def _worker(rank, world, init, out_dir, n_layer, n_chunks, restrict, all_gather=
         if rank == 0:
             np.savez(os.path.join(out_dir, f"{tag}.npz"), losses=np.array(losses), grad0=grad0.numpy(),
                      table=table.numpy(), u_out=u_out.numpy(), i_out=i_out.numpy())
+
+    try:
+        run()
+        # Orderly teardown: the model, its autograd graph and the request handles of its exchanges are released, and every
+        # rank has finished, before any rank closes the group.  Without this a rank now and then aborted in native code at
+        # interpreter exit, after its work was done ("terminate called without an active exception"), on a loaded machine.
+        gc.collect()
+        dist.barrier()
     finally:
         dist.destroy_process_group()
 

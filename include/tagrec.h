@@ -633,8 +633,10 @@ int tagrec_ngcf_wgrad_rows_f32(const float* N, const float* X, const float* dP1,
  * WT = cat(0, ew) W1[D:]  [n_wt, A] (row 0 = pad).  idx / widx: int32 [n, k], neighbour id + 1 and weight
  * index, 0 = pad (a zero row that still takes part in the softmax, as in the reference).
  *   fwd: attn[n,k] = softmax_k( relu(P[v] + WT[widx] + Q[idx-1]) . v );  out[v] = sum_k attn * Ej[idx-1]
- *   bwd: from dOut [n, D]: dP [n, A] (written), dWT [n_wt, A] and dv [A] (written; deterministic fold of
- *        per-block partials; workspace of tagrec_tgcn_attn_workspace(n_wt, A) floats), and EITHER
+ *   bwd: from dOut [n, D]: dP [n, A] (written), dWT [n_wt, A] and dv [A] (written; fixed-order fold of
+ *        per-block partials, which are themselves summed by LDS float atomics in no fixed order: dWT and
+ *        dv agree between runs to rounding, not bit for bit -- dP, dh and comp do bit for bit; workspace
+ *        of tagrec_tgcn_attn_workspace(n_wt, A) floats), and EITHER
  *        dh = NULL: dQ [m, A] and dEj [m, D] by float-atomic scatter-add into caller-zeroed buffers, OR
  *        dh [n, k, A] (written): the per-(node, neighbour) pre-activation gradients; the caller then forms
  *        dQ = S dh and dEj = G dOut as pull products over the inverted neighbour table with tagrec_spmm_f32

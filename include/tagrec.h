@@ -252,18 +252,28 @@ int tagrec_noise_dir_f32(float* out, const int64_t* node_ids, int64_t n_rows, ui
  *   batch_hop_plan   : gt = the TRANSPOSE of A (A itself when A is symmetric); rows = the n_listed (<= 16384) batch rows,
  *                      int64, may repeat (a node counts once).  Builds, on the stream and without a host read, one record
  *                      (destination j, source b, weight) per stored entry of a listed row of gt, grouped by destination
- *                      and ordered by ascending source inside a destination (integer atomics only; the order does not
- *                      depend on them).  `capacity` bounds the record count (the sum of the n_listed largest row degrees
+ *                      and ordered by ascending source inside a destination (a counting sort by destination in LDS; the
+ *                      order does not depend on its integer atomics), and the list of rows the hop visits: every destination with a record and every
+ *                      listed row without one, each once, with its device-side length (the work of plan and hop follows
+ *                      the records, not the rows of gt, which must be square with at most 2^24 rows).  `capacity` bounds the record count (the
+ *                      sum of the n_listed largest row degrees
  *                      of gt always suffices); records beyond it are dropped -- never written -- and *err |= 1; a listed
  *                      id outside gt's rows is skipped and *err |= 2.  err is only ever set, the caller clears it.
  *                      ws: tagrec_batch_hop_workspace(n_rows, n_listed, capacity) bytes, 256-byte aligned.
  *   batch_hop_normbwd: tagrec_spmm_normbwd_sparse_f32(in_flags = the listed rows, in_count = NULL, row_mask) from that
- *                      plan.  A row of row_mask is written when it has a record or its dz_flags byte is set (NULL = every
- *                      row); the others are left untouched, G_out and out_flags alike.  Rows of A with at most 1024 stored
+ *                      plan.  A row of row_mask is written when it has a record, or is a listed row whose dz_flags byte is
+ *                      set (NULL = every listed row); the others are left untouched, G_out and out_flags alike.  The launch
+ *                      is a fixed grid that strides over the plan's row list, tagrec_batch_hop_grid_rows(D) rows per pass
+ *                      (0: D not supported).  Rows of A with at most 1024 stored
  *                      entries get the bits of the masked kernel (the same fused multiply-adds in the same order); longer
  *                      rows are summed in ascending source order as well, in fp64 rounded once, where the masked kernel
  *                      folds chunk partials (last bits may differ; no further from the exact sum). */
 int64_t tagrec_batch_hop_workspace(int64_t n_rows, int64_t n_listed, int64_t capacity);
+int tagrec_batch_hop_grid_rows(int D);
+/* where a built plan keeps its row list inside ws -- what = 0: byte offset of its device-side length (int32, may exceed the
+ * capacity after an overflow), 1: byte offset of the list (four int32 per row: row id, start and length of its record
+ * segment, unused), 2: its capacity in rows; -1: bad arguments */
+int64_t tagrec_batch_hop_list_result(int64_t n_rows, int64_t n_listed, int64_t capacity, int what);
 int tagrec_batch_hop_plan(const tagrec_graph* gt, const int64_t* rows, int64_t n_listed, int64_t capacity, void* ws,
                           int64_t ws_bytes, int32_t* err, void* stream);
 int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* ws, int64_t ws_bytes, int64_t n_listed, int64_t capacity,
@@ -581,6 +591,15 @@ int tagrec_spmm_axpy_adam_graph_f32(const tagrec_graph* g, const float* G_in, co
  * gradient of a table that several consumers read (what autograd's pairwise accumulation does in 3 passes per extra
  * gradient).  `srcs` is a HOST array of device pointers; `out` may alias a source. */
 int tagrec_sum_n_f32(float* out, const float* const* srcs, int n_srcs, int64_t n, void* stream);
+
+/* The layer mean of a restricted LightGCN step on its n_listed batch rows, and their ego rows, in one launch:
+ *   out_b[k] = s x0[rows[k]] + sum_l s y[l][rows[k]] inv[l][rows[k]] + s z_top[k],   ego_b[k] = x0[rows[k]]  (ego_b may be NULL)
+ * x0, y[l]: [n_rows, D]; inv[l]: [n_rows]; z_top, out_b, ego_b: [n_listed, D]; D a multiple of 4; 0 <= n_layers <= 8.
+ * `y` and `inv` are HOST arrays of device pointers.  Same operation order and roundings as torch's index_select, `* s`,
+ * addcmul_(value = s) per layer and add_(alpha = s): the same bits.  A row id outside [0, n_rows) yields NaN rows. */
+int tagrec_layer_mean_rows_f32(const float* x0, const int64_t* rows, int64_t n_listed, int64_t n_rows, const float* const* y,
+                               const float* const* inv, int n_layers, const float* z_top, float s, float* out_b, float* ego_b,
+                               int D, void* stream);
 
 /* ---- NGCF layer, dense half (ngcf.py:77-86), exact-fp32 MFMA ------------------------------------------
  * Given N = A @ X (tagrec_spmm_f32) and W1p = W1 + b1, W2p = W2 + b2 (row-major [Din, Dout]; the

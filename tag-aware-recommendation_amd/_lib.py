@@ -183,6 +183,8 @@ _SIGNATURES = {
                                      c_void_p, c_int, c_void_p],
     "tagrec_noise_dir_f32": [c_void_p, c_void_p, c_int64, ctypes.c_uint64, c_int, c_int, c_int, c_void_p],
     "tagrec_batch_hop_workspace": [c_int64, c_int64, c_int64],
+    "tagrec_batch_hop_grid_rows": [c_int],
+    "tagrec_batch_hop_list_result": [c_int64, c_int64, c_int64, c_int],
     "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
     "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
@@ -235,6 +237,8 @@ _SIGNATURES = {
     "tagrec_spmm_axpy_adam_graph_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
     "tagrec_sum_n_f32": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
+    "tagrec_layer_mean_rows_f32": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p,
+                                   c_void_p, c_int, c_void_p],
     "tagrec_adam_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int64,
                         c_void_p],
     "tagrec_adam_multi_f32": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64, c_void_p],

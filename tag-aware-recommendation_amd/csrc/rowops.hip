@@ -1102,6 +1102,70 @@ extern "C" int tagrec_row_flags_f32(const float* X, int64_t n_rows, int D, uint8
   return count_flags(row_flags, n_rows, count, s);
 }
 
+// ---- the layer mean of a restricted step on its T batch rows, in ONE launch ------------------------------------------------
+//   out_b[k] = s x0[rows[k]] + s y_0[rows[k]] inv_0[rows[k]] + ... + s z_top[k],   ego_b[k] = x0[rows[k]]
+// in the order and with the roundings of the torch sequence it replaces (index_select, `* s`, addcmul_(value = s) per stored
+// layer, add_(alpha = s)): torch's addcmul evaluates fma(s, rn(y inv), acc) and its add fma(s, z, acc) on this platform, and
+// so does this kernel -- the same bits.  One thread per float4; an id outside the table yields NaN rows.
+namespace tagrec {
+constexpr int kMaxMeanLayers = 8;
+struct MeanLayers {
+  const float4* y[kMaxMeanLayers];
+  const float* inv[kMaxMeanLayers];
+};
+__global__ __launch_bounds__(kThreads) void layer_mean_rows_kernel(const float4* __restrict__ x0, const int64_t* __restrict__ rows,
+                                                                   int64_t n_rows, MeanLayers ly, int n_layers,
+                                                                   const float4* __restrict__ z_top, float s, float4* __restrict__ out_b,
+                                                                   float4* __restrict__ ego_b, int64_t n4, int D4) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n4) return;
+  const int64_t r = rows[i / D4];
+  if (r < 0 || r >= n_rows) {
+    const float nan = __int_as_float(0x7fc00000);
+    out_b[i] = make_float4(nan, nan, nan, nan);
+    if (ego_b) ego_b[i] = make_float4(nan, nan, nan, nan);
+    return;
+  }
+  const int64_t at = r * D4 + i % D4;
+  const float4 x = x0[at];
+  if (ego_b) ego_b[i] = x;
+  float4 o = make_float4(__fmul_rn(x.x, s), __fmul_rn(x.y, s), __fmul_rn(x.z, s), __fmul_rn(x.w, s));
+  for (int l = 0; l < n_layers; ++l) {
+    const float4 y = ly.y[l][at];
+    const float inv = ly.inv[l][r];
+    o.x = fmaf(s, __fmul_rn(y.x, inv), o.x); o.y = fmaf(s, __fmul_rn(y.y, inv), o.y);
+    o.z = fmaf(s, __fmul_rn(y.z, inv), o.z); o.w = fmaf(s, __fmul_rn(y.w, inv), o.w);
+  }
+  const float4 z = z_top[i];
+  out_b[i] = make_float4(fmaf(s, z.x, o.x), fmaf(s, z.y, o.y), fmaf(s, z.z, o.z), fmaf(s, z.w, o.w));
+}
+}  // namespace tagrec
+
+extern "C" int tagrec_layer_mean_rows_f32(const float* x0, const int64_t* rows, int64_t n_listed, int64_t n_rows,
+                                          const float* const* y, const float* const* inv, int n_layers, const float* z_top,
+                                          float s, float* out_b, float* ego_b, int D, void* stream) {
+  TAGREC_REQUIRE(x0 && rows && z_top && out_b, "layer_mean_rows: null pointer");
+  TAGREC_REQUIRE(n_listed >= 0 && n_rows >= 1 && D >= 4 && D % 4 == 0, "layer_mean_rows: bad shape (D must be a multiple of 4)");
+  TAGREC_REQUIRE(n_layers >= 0 && n_layers <= tagrec::kMaxMeanLayers && (n_layers == 0 || (y && inv)),
+                 "layer_mean_rows: 0 .. 8 stored layers expected");
+  TAGREC_REQUIRE(aligned16(x0) && aligned16(z_top) && aligned16(out_b) && aligned16(ego_b), "layer_mean_rows: rows must be 16-byte aligned");
+  tagrec::MeanLayers ly{};
+  for (int l = 0; l < n_layers; ++l) {
+    TAGREC_REQUIRE(y[l] && inv[l] && aligned16(y[l]), "layer_mean_rows: null or unaligned layer");
+    ly.y[l] = reinterpret_cast<const float4*>(y[l]);
+    ly.inv[l] = inv[l];
+  }
+  if (n_listed == 0) return TAGREC_OK;
+  const int D4 = D / 4;
+  const int64_t n4 = n_listed * D4;
+  tagrec::layer_mean_rows_kernel<<<static_cast<unsigned>((n4 + tagrec::kThreads - 1) / tagrec::kThreads), tagrec::kThreads, 0,
+                                   static_cast<hipStream_t>(stream)>>>(
+      reinterpret_cast<const float4*>(x0), rows, n_rows, ly, n_layers, reinterpret_cast<const float4*>(z_top), s,
+      reinterpret_cast<float4*>(out_b), reinterpret_cast<float4*>(ego_b), n4, D4);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
 // ---- out = s_0 + s_1 + ... + s_{k-1} in ONE pass (k <= 8), summed left to right --------------------------------------
 // A table read by several consumers (TGCN: the Q projection, two neighbour attentions, the node's own slot) receives
 // one gradient per consumer; autograd adds them pairwise -- three passes over the table per extra gradient.  Here the

@@ -492,6 +492,7 @@ class Graph:
                    _lib.stream_ptr())
 
     BATCH_HOP_MAX_LISTED = 16384      # what tagrec_batch_hop_plan accepts
+    BATCH_HOP_MAX_ROWS = 1 << 24
 
     def batch_hop_capacity(self, n_listed):
         """Upper bound of the records `batch_hop_plan` can produce for ANY list of n_listed rows of this matrix: the sum of
@@ -513,10 +514,16 @@ class Graph:
             raise _lib.TagrecError("batch_hop_workspace: " + _lib.load().tagrec_last_error().decode("utf-8", "replace"))
         return nb + 256
 
+    @staticmethod
+    def batch_hop_grid_rows(D):
+        """Rows one pass of `batch_hop_normbwd`'s fixed grid takes from the plan's row list at width D (it strides over the rest)."""
+        return int(_lib.load().tagrec_batch_hop_grid_rows(int(D)))
+
     def batch_hop_plan(self, rows, capacity, buf):
         """The inverted list of the stored entries of `rows` (int64 node ids, may repeat) of THIS matrix, for the hop of its
         transpose (`Graph.batch_hop_normbwd` of `self.transpose()`): records grouped by destination = column, ascending
-        source = row inside a destination.  buf: uint8 [>= batch_hop_workspace(len(rows), capacity)], owned by the caller
+        source = row inside a destination, and the list of rows the hop visits (every destination with a record, every listed
+        row without one).  buf: uint8 [>= batch_hop_workspace(len(rows), capacity)], owned by the caller
         (the step workspace).  Device only; an overflow of `capacity` is reported by `batch_hop_check`."""
         rows = rows.contiguous()
         _lib.require_gpu_tensor(rows, torch.int64, "batch_hop_plan rows")
@@ -528,6 +535,18 @@ class Graph:
         self._call("batch_hop_plan", _lib.load().tagrec_batch_hop_plan, self._h, _lib.ptr(rows), rows.numel(), int(capacity),
                    _lib.c_void_p(buf.data_ptr() + off), nbytes, _lib.ptr(self._hop_err), _lib.stream_ptr())
         return (buf, buf.data_ptr() + off, nbytes, rows.numel(), int(capacity))
+
+    def batch_hop_rows(self, plan):
+        """The rows the hop of `plan` visits, int32, in the plan's (arbitrary) order: a view into the plan's buffer (the first
+        word of its (row, segment start, segment length, -) entries).  Reads the
+        list's device-side length on the host (synchronises): for tests and diagnostics, no step calls it."""
+        buf, ptr, _, n_listed, capacity = plan
+        at = [int(_lib.load().tagrec_batch_hop_list_result(self.shape[1], n_listed, capacity, k)) for k in range(3)]
+        if min(at) < 0:
+            raise _lib.TagrecError("batch_hop_rows: " + _lib.load().tagrec_last_error().decode("utf-8", "replace"))
+        base = ptr - buf.data_ptr()
+        n = int(buf[base + at[0]:base + at[0] + 4].view(torch.int32).item())
+        return buf[base + at[1]:base + at[1] + 16 * min(n, at[2])].view(torch.int32).view(-1, 4)[:, 0]
 
     def batch_hop_check(self):
         """Host-side check of the plans built from this matrix so far (synchronises): raises if one overflowed its capacity
@@ -541,8 +560,8 @@ class Graph:
 
     def batch_hop_normbwd(self, plan, g_in, x_raw, inv_norm, dz, d_scale, g_out, out_flags, row_mask, dz_flags=None):
         """`spmm_normbwd_sparse(in_flags = the plan's rows, in_count = None, row_mask = row_mask)` from the inverted list
-        `plan` (`self.transpose().batch_hop_plan(rows, ...)`).  Rows of row_mask that have no record and no dz_flags byte
-        are left untouched (g_out unwritten, out_flags as the caller zeroed it)."""
+        `plan` (`self.transpose().batch_hop_plan(rows, ...)`).  Rows of row_mask that have no record and are no listed row
+        with a dz_flags byte (None: every listed row) are left untouched (g_out unwritten, out_flags as the caller zeroed it)."""
         D = self._chk_x(g_in, self.shape[1], "batch_hop_normbwd g_in")
         for t, nm in ((x_raw, "x_raw"), (dz, "dz"), (g_out, "g_out")):
             if self._chk_x(t, self.shape[0], "batch_hop_normbwd " + nm) != D:

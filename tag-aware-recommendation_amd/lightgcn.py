@@ -122,12 +122,13 @@ def spmm_listed(graph, rows, x, out=None):
     return graph.spmm_listed(rows, x, out)
 
 
-def restricted_forward(graph, x0, n_layer, rows, ws=None):
+def restricted_forward(graph, x0, n_layer, rows, ws=None, want_ego=False):
     """The forward pass of a training step whose loss reads the layer mean at `rows` (int64 node ids [T], may repeat)
     only -- the BPR batch rows (lightgcn.py:71-75).  Layers below L-1 run on all rows (through the popular items every
     row is within two hops of the batch), layer L-1 on the batch rows and their neighbours (row-masked kernel), layer L
     in compact form on the batch rows alone (`spmm_listed`); no layer accumulates the mean, which is formed at the end
-    on the T rows.  Returns (out_b [T, D], state for `restricted_backward`).  Rows a layer did not compute are left
+    on the T rows by one row kernel (`rowops.layer_mean_rows`), which also gathers the ego rows x0[rows] when want_ego.
+    Returns (out_b [T, D], state for `restricted_backward`[, ego_b [T, D]]).  Rows a layer did not compute are left
     UNWRITTEN in its output; every later reader is told which rows are valid."""
     L, s = n_layer, 1.0 / (n_layer + 1)
     n, D = x0.shape
@@ -144,11 +145,9 @@ def restricted_forward(graph, x0, n_layer, rows, ws=None):
         x = y
     y_top = spmm_listed(graph, rows, x)
     z_top, inv_top = rowops.rownorm_fwd(y_top)
-    out_b = x0.index_select(0, rows) * s
-    for y, inv in zip(raws, invs):
-        out_b.addcmul_(y.index_select(0, rows), inv.index_select(0, rows)[:, None], value=s)
-    out_b.add_(z_top, alpha=s)
-    return out_b, (raws, invs, mid, y_top, inv_top)
+    out_b, ego_b = rowops.layer_mean_rows(x0, rows, raws, invs, z_top, s, want_ego)
+    state = (raws, invs, mid, y_top, inv_top)
+    return (out_b, state, ego_b) if want_ego else (out_b, state)
 
 
 # The masked hop of `restricted_backward` from an inverted list of the batch rows' entries (Graph.batch_hop_plan) instead of a
@@ -158,13 +157,14 @@ BATCH_HOP_LIST = True
 
 def batch_hop_plan(graph_t, rows, ws=None):
     """The per-step plan of the list-driven masked hop of A = graph_t, or None where the masked row kernel serves better:
-    a list longer than the plan kernel takes, or a record bound -- the sum of the len(rows) largest row degrees, cached on
+    a list or a matrix larger than the plan kernels take, or a record bound -- the sum of the len(rows) largest row degrees, cached on
     the graph -- above a quarter of the stored entries (the plan's buffers would rival the matrix)."""
     if isinstance(graph_t, EdgeDropView):     # edge dropout: the list-driven hop has no edge-drop form; the masked row kernel has
         return None
     src = graph_t.transpose()                 # its batch rows store exactly the entries of A that point at a batch row
     T = rows.numel()
-    if not BATCH_HOP_LIST or T < 1 or T > Graph.BATCH_HOP_MAX_LISTED or src.shape[0] != src.shape[1]:
+    if (not BATCH_HOP_LIST or T < 1 or T > Graph.BATCH_HOP_MAX_LISTED or src.shape[0] != src.shape[1]
+            or src.shape[0] > Graph.BATCH_HOP_MAX_ROWS):
         return None
     cap = src.batch_hop_capacity(T)
     if cap < 1 or cap > src.nnz // 4:
@@ -277,8 +277,7 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
                            and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
         if ctx.compact:
-            out_b, ctx.state = restricted_forward(graph, x0, n_layer, rows, ctx.ws)
-            ego_b = x0.index_select(0, rows)
+            out_b, ctx.state, ego_b = restricted_forward(graph, x0, n_layer, rows, ctx.ws, want_ego=True)
             ctrip = rowops.compact_triplets(B, x0.device)
             res, ctx.coef = rowops.bpr_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip, loss_kind)
             ctx.rows, ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.shape = rows, out_b, ego_b, ctrip, x0.shape
@@ -311,13 +310,13 @@ class _PropagateBprLoss(torch.autograd.Function):
         ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
                            and rows.numel() * 16 <= n)              # a batch that touches most rows gains nothing
         if ctx.compact:
-            out_b, ctx.state = restricted_forward(graph, x0, n_layer, rows, ctx.ws)
+            out_b, ctx.state, ego_b = restricted_forward(graph, x0, n_layer, rows, ctx.ws, want_ego=True)
         else:
             ctx.masks = {}
             out, ctx.raws, ctx.invs = propagate_forward(graph, x0, n_layer, drops, seed, rows if restrict else None, ctx.masks)
             ctx.drops, ctx.seed = drops, seed
             out_b = out.index_select(0, rows)
-        ego_b = x0.index_select(0, rows)
+            ego_b = x0.index_select(0, rows)
         ctx.in_batch = None
         if isinstance(rank, H.InBatchRoute):
             res, ctx.in_batch = H.in_batch_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])

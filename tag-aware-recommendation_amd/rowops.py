@@ -67,6 +67,27 @@ def rownorm_bwd(x_raw, inv, dz, s, out, accumulate=False):
     return out
 
 
+def layer_mean_rows(x0, rows, raws, invs, z_top, s, want_ego=True):
+    """The layer mean of a restricted step on its batch rows, in one launch -> (out_b, ego_b or None), both [T, D]:
+    out_b = s x0[rows] + sum_l s raws[l][rows] invs[l][rows, None] + s z_top, ego_b = x0[rows] -- the bits of the torch
+    sequence index_select / `* s` / addcmul_(value=s) per layer / add_(alpha=s).  rows int64 [T] (may repeat); D % 4 == 0."""
+    T, D = z_top.shape
+    for t, nm in [(x0, "x0"), (z_top, "z_top")] + [(y, "raws") for y in raws] + [(v, "invs") for v in invs]:
+        _lib.require_gpu_tensor(t, torch.float32, "layer_mean_rows: " + nm)
+    _lib.require_gpu_tensor(rows, torch.int64, "layer_mean_rows: rows")
+    n = x0.shape[0]
+    if (rows.shape != (T,) or x0.shape[1] != D or len(raws) != len(invs) or len(raws) > 8 or D % 4
+            or any(y.shape != x0.shape for y in raws) or any(v.shape != (n,) for v in invs)):
+        raise _lib.TagrecError("layer_mean_rows: x0 / raws [n, D], invs [n], z_top [T, D], rows [T], D % 4 == 0, <= 8 layers expected")
+    out_b = torch.empty(T, D, dtype=torch.float32, device=x0.device)
+    ego_b = torch.empty(T, D, dtype=torch.float32, device=x0.device) if want_ego else None
+    ys = (_lib.c_void_p * max(len(raws), 1))(*[y.data_ptr() for y in raws])
+    vs = (_lib.c_void_p * max(len(invs), 1))(*[v.data_ptr() for v in invs])
+    check(load().tagrec_layer_mean_rows_f32(ptr(x0), ptr(rows), T, n, ys, vs, len(raws), ptr(z_top), float(s), ptr(out_b),
+                                            ptr(ego_b), D, stream_ptr()), "layer_mean_rows")
+    return out_b, ego_b
+
+
 def _flags_count(n, device, flags, count):
     if flags is None:
         flags = torch.empty(n, dtype=torch.uint8, device=device)

@@ -424,6 +424,34 @@ int tagrec_inbatch_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
                            int64_t B, float temperature, const float* lse, const float* g,
                            float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
 
+/* ---- DirectAU on COMPACT rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
+ * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub; repeated rows are kept.
+ * Ureg / Ireg [B, Dreg] (stride ldreg): the rows the L2 term reads (both NULL: no L2 term).  x^ = x / max(|x|, 1e-12).
+ *   align   = (1 / B) sum_b |u^_b - i^_b|^2                                   (difference form)
+ *   S(X)    = sum_{i < j} expf(2 t (x^_i . x^_j - 1))                         (exact-fp32 MFMA 16x16x4 scores; = exp(-t |x^_i - x^_j|^2))
+ *   unif(X) = logf(S(X)) + log(2 / (B (B - 1)))                               (the constant in double on the host)
+ * fwd writes loss_out[0] = align + gamma (unif(U) + unif(I)) / 2, loss_out[1] = 0.5 sum |row|^2 / B over the 2 B L2 rows
+ * (unweighted), parts[3] = [align, unif(U), unif(I)] and the state the backward reads: inv [2 B] (the inverse norms of the
+ * rows of Ub, then of Ib) and ls [2] = logf(S) of the two sides.  `partials`: scratch of 2 ceil(B / 4) + 2 ceil(B / 64)
+ * floats; every reduction runs in a fixed order (no atomics).  D must be a multiple of 4 in 8 .. 256 and 2 <= B <= 65536
+ * (TAGREC_E_UNSUPPORTED otherwise); 0 < t <= 20 -- a term is then >= e^-80, a normal float, which is what lets the sum run
+ * without a running maximum -- and gamma finite and >= 0 (TAGREC_E_INVALID otherwise). */
+int tagrec_directau_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                            const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                            int64_t B, float t, float gamma,
+                            float* inv, float* ls, float* partials, float* parts, float* loss_out, void* stream);
+/* bwd STORES (no atomics, no read of the old contents; the summation order is a function of (B, D) only) every row of the
+ * gradients with respect to the RAW rows:
+ *   G_i        = sum_{j != i} C_ij x^_j (ascending j) +- g0 (2 / B) (u^_b - i^_b),  C_ij = g0 gamma t expf(2 t (s_ij - 1) - ls)
+ *   dX[i]      = inv_i (G_i - x^_i (x^_i . G_i))
+ *   dXreg[row] = g1 / B * Xreg[row]               for the 2 B L2 rows (dUreg = dIreg = NULL: not written)
+ * g = device pointer to two floats (upstream gradients of the two loss parts) or NULL for (1, 1).  dUreg = dUb and
+ * dIreg = dIb (one buffer for both parts) is allowed when Ureg = Ub, Ireg = Ib with the same stride and width. */
+int tagrec_directau_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                            const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                            int64_t B, float t, float gamma, const float* inv, const float* ls, const float* g,
+                            float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
+
 /* ---- N4: propagation with dynamic per-factor edge weights (DGCF model/dgcf.py:70-110, DisenGCN model/disengcn.py:23-46) --
  * The graph handle supplies the STRUCTURE (rowptr / colidx; its values are not read).  K factors own the column
  * slices [k D/K, (k+1) D/K) of an embedding row (torch.split / torch.cat along dim 1 in the reference).  Per-entry

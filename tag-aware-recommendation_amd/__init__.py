@@ -11,6 +11,7 @@ Reference name                      here
   model.DGCF / DisenGCN / KGAT        tagrec_amd.DGCF / DisenGCN / KGAT
   model.DisenHAN                      tagrec_amd.DisenHAN (disenhan_config(**kw))
   -- (not in the reference)           tagrec_amd.SimGCL: LightGCN + contrastive noise views (get_config("simgcl"))
+  -- (not in the reference)           tagrec_amd.DirectAU: LightGCN under the alignment / uniformity loss (get_config("directau"))
   train_data.BPR_training_data        tagrec_amd.BPR_training_data
   training.Basic_train / Basic_test   tagrec_amd.Basic_train / Basic_test
   training.utils.user_group_split     tagrec_amd.user_group_split
@@ -25,6 +26,7 @@ from .evaluate import Basic_test, user_group_split  # noqa: F401
 from .graph import Graph, creat_adj  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
 from .simgcl import SimGCL  # noqa: F401
+from .directau import DirectAU  # noqa: F401
 from .ngcf import NGCF  # noqa: F401
 from .tgcn import TGCN  # noqa: F401
 from .dgcf import DGCF  # noqa: F401

@@ -31,6 +31,9 @@ def refuse_multi_negative(config, what):
     """Models and producers that consume (user, positive, one negative) triplets refuse n_negatives != 1, the "softmax"
     loss and negatives="in_batch" loudly instead of training on the first negative (only the LightGCN and NGCF steps and
     BPR_training_data are covered)."""
+    if config.get("model") == "directau":
+        raise TagrecError(f"{what}: the \"directau\" configuration is not covered (alignment / uniformity loss: tagrec_amd.DirectAU "
+                          "and BPR_training_data only)")
     neg = config.get("negatives", "sampled")
     if neg != "sampled":
         raise TagrecError(f"{what}: negatives={neg!r} is not covered (in-batch negatives: the LightGCN and NGCF steps and "
@@ -83,6 +86,10 @@ _SIGNATURES = {
                                c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_inbatch_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_directau_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]
+                               + [c_void_p] * 6,
+    "tagrec_directau_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]
+                               + [c_void_p] * 8,
     "tagrec_ngcf_wgrad_workspace": [c_int, c_int],
     "tagrec_ngcf_dense_fwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p],

@@ -30,6 +30,9 @@ _BASE = {
     # where a positive's negatives come from (LightGCN, NGCF and BPR_training_data)
     "negatives": "sampled",       # "in_batch": the other positives of the batch (rowops.inbatch_*); batches are [B, 2], nothing is sampled
     "in_batch_logq": False,       # in-batch: subtract log(train degree of the item / train edges) from every column's logit
+    # BPR_training_data: produce [E, 2] = (user, positive) epoch arrays without launching the sampler (the in-batch branch)
+    # for objectives that take no negatives (DirectAU); the other producers do not read it
+    "pair_batches": False,
 }
 NEG_SAMPLING_MODES = ("uniform", "popularity")
 MAX_NEG_CANDIDATES = 16
@@ -54,7 +57,13 @@ _PER_MODEL = {
     # (simgcl.py); cl_rate weighs the term, cl_eps is the length of the per-layer perturbation, cl_temperature its tau
     "simgcl": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100,
                "cl_rate": 0.5, "cl_eps": 0.1, "cl_temperature": 0.2, "use_tag": False},
+    # DirectAU (not in the reference; Wang et al., KDD 2022): LightGCN trained by alignment of the positive pairs plus au_gamma
+    # times the uniformity of the batch's users and items on the unit sphere, Gaussian potential exp(-au_t |x - y|^2)
+    # (directau.py, rowops.directau_*); batches are [B, 2], nothing is sampled
+    "directau": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100,
+                 "au_gamma": 1.0, "au_t": 2.0, "use_tag": False, "pair_batches": True},
 }
+MAX_AU_T = 20.0                   # a term of the uniformity sum is >= e^(-4 au_t): e^-80 is still a normal fp32 number
 
 
 def get_config(model="lightgcn", **overrides):
@@ -70,6 +79,8 @@ def get_config(model="lightgcn", **overrides):
     check_negatives(cfg)
     if model == "simgcl":
         check_contrastive(cfg)
+    if model == "directau":
+        check_alignment(cfg)
     return cfg
 
 
@@ -129,6 +140,18 @@ def check_contrastive(cfg):
     if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < float("inf"):
         raise TagrecError(f"cl_temperature must be a finite number > 0, got {tau!r}")
     return float(rate), float(eps), float(tau)
+
+
+def check_alignment(cfg):
+    """The two DirectAU keys of a config -> (au_gamma, au_t); a bad value is refused: au_gamma finite and >= 0, au_t in
+    (0, 20] (the uniformity kernels sum exp(-au_t |x - y|^2) <= e^(-4 au_t) without a running maximum)."""
+    from ._lib import TagrecError
+    gamma, t = cfg.get("au_gamma", 1.0), cfg.get("au_t", 2.0)
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not 0 <= gamma < float("inf"):
+        raise TagrecError(f"au_gamma must be a finite number >= 0, got {gamma!r}")
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0 < t <= MAX_AU_T:
+        raise TagrecError(f"au_t must be a number in (0, {MAX_AU_T:g}], got {t!r}")
+    return float(gamma), float(t)
 
 
 CFG =get_config("lightgcn")

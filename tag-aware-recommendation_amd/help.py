@@ -295,6 +295,92 @@ def in_batch_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, item_logq=None, plan
     return out[0], out[1]
 
 
+class AuRoute(NamedTuple):
+    """What a fused step is handed in place of `rank_route`'s value by a DirectAU model: the alignment / uniformity loss."""
+    t: float                               # the Gaussian potential exp(-t |x - y|^2) of the uniformity term
+    gamma: float                           # its weight
+
+
+def au_route(model, batch, t=2.0, gamma=1.0):
+    """A DirectAU model takes [B, 2] = (user, positive) batches; any other width is refused.  -> the `AuRoute` of its step."""
+    if batch.dim() != 2 or batch.shape[1] != 2:
+        raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit the alignment / uniformity loss "
+                               "(expected [B, 2] = user, positive; nothing is sampled)")
+    if batch.shape[0] < 2:
+        raise _lib.TagrecError(f"{model}: a batch of one pair (B = 1) has no other pair to be uniform against")
+    return AuRoute(float(t), float(gamma))
+
+
+def au_stage_fwd(route, pairs, Ub, Ib, Ureg, Ireg):
+    """The DirectAU loss stage of a fused step on its gathered rows (users, then positives) -> (res, state); state.parts is
+    the device tensor [align, unif_u, unif_i]."""
+    res, _, state = rowops.directau_fwd(Ub, Ib, Ureg, Ireg, route.t, route.gamma)
+    return res, state
+
+
+def au_stage_bwd(state, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg):
+    """Its backward: one launch stores the gradient rows of both loss parts (`rowops.directau_bwd`)."""
+    rowops.directau_bwd(Ub, Ib, Ureg, Ireg, state, g, dUb, dIb, dUreg, dIreg)
+
+
+class _AlignUniformLoss(torch.autograd.Function):
+    """DirectAU loss on tables + a [B, 2] pair batch: the 2 B rows are gathered, the fused kernels (rowops.directau_fwd /
+    directau_bwd) run on them and the compact gradients are folded back onto the tables.
+    Returns a 5-vector: [mul_loss, l2reg_loss (unweighted), align, unif_u, unif_i]; only the first two carry a gradient."""
+
+    @staticmethod
+    def forward(ctx, U, I, Ureg, Ireg, pairs, t, gamma, plans):
+        for x, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
+            if x is not None and (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2):
+                raise _lib.TagrecError(f"align_uniform_loss: {nm} must be a 2-d float32 GPU tensor")
+        pairs = _lib.require_gpu_tensor(pairs.contiguous(), torch.int64, "align_uniform_loss pairs")
+        au_route("align_uniform_loss", pairs)
+        urows, irows = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+        Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
+        has_reg = Ureg is not None
+        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
+        Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
+        res, parts, ctx.state = rowops.directau_fwd(Ub, Ib, Urb, Irb, t, gamma)
+        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows)
+        ctx.has_reg, ctx.same, ctx.plans = has_reg, same, plans
+        ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
+        return torch.cat([res, parts])
+
+    @staticmethod
+    def backward(ctx, g):
+        Ub, Ib, Urb, Irb, urows, irows = ctx.saved_tensors
+        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
+        dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
+        if ctx.has_reg and ctx.same:
+            Urb, Irb, dUrb, dIrb = Ub, Ib, dUb, dIb        # reg on the same rows: one gradient buffer
+        elif ctx.has_reg:
+            dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
+        else:
+            Urb = Irb = dUrb = dIrb = None
+        rowops.directau_bwd(Ub, Ib, Urb, Irb, ctx.state, g[:2], dUb, dIb, dUrb, dIrb)
+
+        def fold(shape, rows, src, plan):
+            return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
+
+        dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
+        if ctx.has_reg and not ctx.same:
+            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
+        return dU, dI, None, None, None, None, None, None
+
+
+def align_uniform_loss(U, I, Ureg, Ireg, pairs, t=2.0, gamma=1.0, plans=None, parts_out=None):
+    """(mul_loss, l2reg_loss) of a [B, 2] batch (user, positive) under DirectAU (Wang et al., KDD 2022): with x^ the
+    row-normalised rows of the batch (repeated ids kept), mul_loss = mean_b |u^_b - i^_b|^2 + gamma (unif(U) + unif(I)) / 2,
+    unif(X) = log mean_{i < j} exp(-t |x^_i - x^_j|^2); l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg
+    (None: 0).  The B x B potentials are never stored.  0 < t <= 20, B >= 2.
+    plans (`in_batch_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
+    instead of by `index_add_`.  parts_out (a list): receives the detached device tensor [align, unif_u, unif_i]."""
+    out = _AlignUniformLoss.apply(U, I, Ureg, Ireg, pairs, float(t), float(gamma), plans)
+    if parts_out is not None:
+        parts_out.append(out[2:].detach())
+    return out[0], out[1]
+
+
 def triplet_loss(U, I, Ureg, Ireg, trip, loss_func):
     """(mul_loss, l2reg_loss) of a [B,3] triplet batch against user/item tables."""
     if Ureg is not None and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr():

@@ -258,7 +258,8 @@ class _PropagateBprLoss(torch.autograd.Function):
                 fused_opt=None, ws=None, deterministic=False, rank=None):
         x0 = table.detach()
         # rank = (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*);
-        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*)
+        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*);
+        # an H.AuRoute: a [B, 2] pair batch under the alignment / uniformity loss (rowops.directau_*)
         if rank is not None:
             return _PropagateBprLoss._forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active,
                                                    drops, seed, restrict, fused_opt, ws, deterministic, rank)
@@ -295,7 +296,8 @@ class _PropagateBprLoss(torch.autograd.Function):
     @staticmethod
     def _forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, tuples, loss_kind, reg_active, drops, seed, restrict,
                       fused_opt, ws, deterministic, rank):
-        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd`: only the row list changes, T = (2 + K) B (in-batch: K = 0);
+        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd` / `rowops.directau_fwd`: only the row list changes,
+        T = (2 + K) B (pair batches: K = 0);
         everything around it is the triplet step's.  The all-rows path gathers the T rows of `out` (the kernels take compact
         rows only)."""
         ctx.rank = rank
@@ -317,9 +319,12 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.drops, ctx.seed = drops, seed
             out_b = out.index_select(0, rows)
             ego_b = x0.index_select(0, rows)
-        ctx.in_batch = None
+        ctx.in_batch = ctx.au = None
         if isinstance(rank, H.InBatchRoute):
             res, ctx.in_batch = H.in_batch_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
+        elif isinstance(rank, H.AuRoute):
+            res, ctx.au = H.au_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
+            res = torch.cat([res, ctx.au.parts])            # [mul_loss, l2reg, align, unif_u, unif_i]: the last three carry no gradient
         else:
             res, ctx.coef = rowops.rank_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], loss_kind, rank[1])
         ctx.out_b, ctx.ego_b = out_b, ego_b
@@ -330,11 +335,14 @@ class _PropagateBprLoss(torch.autograd.Function):
         out_b, ego_b, rows, B = ctx.out_b, ctx.ego_b, ctx.rows, ctx.B
         d_b = torch.empty_like(out_b)                                      # d / d out_b: every row is stored by the kernel
         d_e = None
-        if ctx.in_batch is not None:  # one launch stores both parts (the L2 rows are folded after the hop, below)
+        if ctx.in_batch is not None or ctx.au is not None:  # one launch stores both parts (the L2 rows are folded after the hop, below)
             d_e = torch.empty_like(ego_b) if ctx.reg_active else None
             reg = (ego_b[:B], ego_b[B:], d_e[:B], d_e[B:]) if ctx.reg_active else (None,) * 4
-            H.in_batch_stage_bwd(ctx.in_batch, out_b[:B], out_b[B:], reg[0], reg[1], g, d_b[:B], d_b[B:], reg[2], reg[3])
-            ctx.in_batch = None
+            if ctx.au is not None:
+                H.au_stage_bwd(ctx.au, out_b[:B], out_b[B:], reg[0], reg[1], g[:2], d_b[:B], d_b[B:], reg[2], reg[3])
+            else:
+                H.in_batch_stage_bwd(ctx.in_batch, out_b[:B], out_b[B:], reg[0], reg[1], g, d_b[:B], d_b[B:], reg[2], reg[3])
+            ctx.in_batch = ctx.au = None
         else:
             rowops.rank_bwd(out_b[:B], out_b[B:], None, None, ctx.coef, g, d_b[:B], d_b[B:], None, None)
         if ctx.compact:
@@ -478,13 +486,16 @@ class LightGCN(FusedStepModel):
     def forward(self):
         return self._split(self._propagate())
 
+    def _route(self, batch_data):
+        """The loss stage of this model's step for `batch_data` (a subclass with another objective overrides it)."""
+        if self.in_batch:
+            return H.in_batch_route(type(self).__name__, batch_data, self.loss_temperature, self.item_logq)
+        return H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
-        if self.in_batch:
-            rank = H.in_batch_route(type(self).__name__, batch_data, self.loss_temperature, self.item_logq)
-        else:
-            rank = H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+        rank = self._route(batch_data)
         if self._fused_ok():
             graph = self._graph()                       # (first: kernel-mode edge dropout refuses a capture before any launch)
             drops, seed = self._drops()
@@ -493,12 +504,19 @@ class LightGCN(FusedStepModel):
                                           H.loss_kind_id(self.loss_func), self.reg != 0, drops, seed, self.restrict_forward,
                                           fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None,
                                           self.deterministic, rank)
+            if isinstance(rank, H.AuRoute):
+                self.last_au_parts = res[2:].detach()
             return res[0], self.reg * res[1]
         if self.deterministic:
             raise _lib.TagrecError("LightGCN: deterministic=True covers the fused step only (no row folds: split_adj_k == 1)")
         all_users, all_items = self.forward()[:2]
         ego = self.embed
-        if self.in_batch:
+        if isinstance(rank, H.AuRoute):
+            parts = []
+            loss, reg_loss = H.align_uniform_loss(all_users, all_items, ego[0], ego[1], batch_data, rank.t, rank.gamma, parts_out=parts)
+            self.last_au_parts = parts[0]
+            return loss, self.reg * reg_loss
+        if isinstance(rank, H.InBatchRoute):
             loss, reg_loss = H.in_batch_loss(all_users, all_items, ego[0], ego[1], batch_data, rank.temperature, rank.item_logq)
             return loss, self.reg * reg_loss
         if rank is not None:

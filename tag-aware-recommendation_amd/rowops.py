@@ -300,6 +300,66 @@ def inbatch_bwd(Ub, Ib, Ureg, Ireg, temperature, lse, g, dUb, dIb, dUreg, dIreg,
                                         ptr(dIreg), stream_ptr()), what)
 
 
+# ---- DirectAU on compact rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
+
+AU_PREP_ROWS = 4         # batch positions per block of the prep kernel: `partials` holds two floats per block of it ...
+AU_TILE = 64             # ... and one per side and block of the uniformity kernel
+
+
+class AuState:
+    """What `directau_fwd` keeps for `directau_bwd`: t, gamma, inv [2 B] (inverse row norms of Ub, then Ib), ls [2] = log S;
+    parts = the forward's [align, unif_u, unif_i] (not read by the backward)."""
+    __slots__ = ("t", "gamma", "inv", "ls", "parts")
+
+    def __init__(self, t, gamma, inv, ls, parts):
+        self.t, self.gamma, self.inv, self.ls, self.parts = t, gamma, inv, ls, parts
+
+
+def _au_args(what, Ub, Ib, Ureg, Ireg):
+    B = _inbatch_args(what, Ub, Ib, Ureg, Ireg, None, None, None)
+    if B < 2:
+        raise _lib.TagrecError(f"{what}: a batch of one pair (B = 1) has no other pair to be uniform against")
+    return B
+
+
+def directau_fwd(Ub, Ib, Ureg, Ireg, t, gamma):
+    """DirectAU loss of B (user, positive) pairs on gathered rows: align + gamma (unif(Ub) + unif(Ib)) / 2 on the row-normalised
+    operands (include/tagrec.h has the formulas); Ureg / Ireg: the L2 rows (None: no L2 term).
+    -> (res = [mul_loss, l2reg_loss (unweighted)], parts = [align, unif_u, unif_i], state for `directau_bwd`).
+    The B x B Gaussian potentials are never stored."""
+    B = _au_args("directau_fwd", Ub, Ib, Ureg, Ireg)
+    ld, D = _pair_ld("directau_fwd", ("Ub", "Ib"), Ub, Ib)
+    ldreg, dreg = _pair_ld("directau_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
+    dev = Ub.device
+    inv = torch.empty(2 * B, dtype=torch.float32, device=dev)
+    small = torch.empty(7, dtype=torch.float32, device=dev)              # ls [2] | parts [3] | res [2]
+    ls, parts, res = small[0:2], small[2:5], small[5:7]
+    partials = torch.empty(2 * ((B + AU_PREP_ROWS - 1) // AU_PREP_ROWS) + 2 * ((B + AU_TILE - 1) // AU_TILE), dtype=torch.float32,
+                           device=dev)
+    check(load().tagrec_directau_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, float(t), float(gamma),
+                                         ptr(inv), ptr(ls), ptr(partials), ptr(parts), ptr(res), stream_ptr()), "directau_fwd")
+    return res, parts, AuState(float(t), float(gamma), inv, ls, parts)
+
+
+def directau_bwd(Ub, Ib, Ureg, Ireg, state, g, dUb, dIb, dUreg, dIreg, what="directau_bwd"):
+    """STORES the gradients of `directau_fwd`'s two loss parts with respect to the RAW rows (g = their upstream gradients, two
+    floats; None: both 1) into every row of dUb / dIb and dUreg / dIreg -- no atomics, the old contents are not read.
+    dUreg = dIreg = None: the L2 gradient is not written; dUreg is dUb and dIreg is dIb (with Ureg is Ub, Ireg is Ib): one
+    buffer takes the sum."""
+    B = _au_args(what, Ub, Ib, Ureg, Ireg)
+    g = None if g is None else g.contiguous()
+    ld, D = _pair_ld(what, ("Ub", "Ib"), Ub, Ib, (dUb, dIb))
+    ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
+    inv, ls = state.inv, state.ls
+    if inv.shape != (2 * B,) or not inv.is_contiguous() or inv.dtype != torch.float32 or ls.shape != (2,) or ls.dtype != torch.float32:
+        raise _lib.TagrecError(f"{what}: the state must hold a contiguous float32 inv [{2 * B}] and ls [2]")
+    for nm, t in (("dUb", dUb), ("dIb", dIb), ("dUreg", dUreg), ("dIreg", dIreg)):
+        if t is not None and t.shape[0] != B:
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {B} rows")
+    check(load().tagrec_directau_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, state.t, state.gamma,
+                                         ptr(inv), ptr(ls), ptr(g), ptr(dUb), ptr(dIb), ptr(dUreg), ptr(dIreg), stream_ptr()), what)
+
+
 def fold_rows(dst, rows, src, plan=None, accumulate=True):
     """dst[rows[j]] (+)= src[j]: through `plan` (the `row_list_plan` of rows) in a fixed order, else by `index_add_` (float
     atomics where the list names a row twice).  Without `accumulate` the listed rows of dst are overwritten with their sums."""

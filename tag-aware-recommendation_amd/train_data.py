@@ -164,7 +164,8 @@ def _sampler_keys(cfg, pos):
 
 class BPR_training_data(Abstract_training_data):
     """config["n_negatives"] = K negatives per train edge (default one: [E, 3] triplets; else [E, 2 + K] tuples), re-drawn
-    and shuffled every epoch; config["negatives"] = "in_batch": [E, 2] pairs, nothing is drawn, the shuffle is the same.
+    and shuffled every epoch; config["negatives"] = "in_batch" or config["pair_batches"] = True: [E, 2] pairs, nothing is
+    drawn, the shuffle is the same.
     With config["neg_candidates"] > 1 the epoch's
     negatives are scored by `model` (given here or through `attach_model`): one eval-mode, no-grad `model.forward()` per
     epoch supplies the user and item tables `predict_rating` scores with."""
@@ -181,7 +182,11 @@ class BPR_training_data(Abstract_training_data):
         self._alias, self._n_cand = _sampler_keys(cfg, self._pos)
         self._n_neg = check_ranking(cfg)[0]          # K negatives per edge: the epoch array is [E, 2 + K]
         # negatives="in_batch": the epoch array is [E, 2], the sampler is not launched (so no model is needed either)
-        self._in_batch = check_negatives(cfg)[0]
+        # pair_batches=True (DirectAU: an objective without negatives) takes the same branch
+        pair = cfg.get("pair_batches", False)
+        if not isinstance(pair, bool):
+            raise _lib.TagrecError(f"pair_batches must be True or False, got {pair!r}")
+        self._in_batch = check_negatives(cfg)[0] or pair
         self._model = model
         self._seed = int(cfg["seed"] if seed is None else seed)
         self._epoch = 0

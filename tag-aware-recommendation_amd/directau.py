@@ -14,8 +14,9 @@ x^ = x / max(|x|, 1e-12):
     mul_loss = align + au_gamma (unif(U) + unif(I)) / 2
 
 The loss stage is `rowops.directau_fwd` / `directau_bwd` (csrc/directau.hip: the B x B potentials are never stored, no float
-atomics) and it sits where the in-batch softmax sits in LightGCN's own autograd node (`lightgcn._PropagateBprLoss`, an
-`help.AuRoute` in place of the in-batch route), so everything around it is LightGCN's: the compact restricted step and the
+atomics), wrapped as the `Au` stage of loss_stage.py: `_route` returns an `help.AuRoute`, `help.stage_for` turns it into the
+stage, and LightGCN's own autograd node (`lightgcn._PropagateBprLoss`) runs its one forward and backward around it as around
+any other stage.  So everything around the loss is LightGCN's: the compact restricted step and the
 all-rows path, deterministic=True, Adam.fuse_into, GraphedStep replay, the step workspace, message dropout and both
 edge-dropout modes.  Batches come from `BPR_training_data` with config["pair_batches"] = True (the "directau" default)."""
 from . import _lib, help as H

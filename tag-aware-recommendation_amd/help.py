@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib, rowops
+from . import _lib, loss_stage as S, rowops
 from .cor import cor_loss  # noqa: F401  (the distance-correlation penalty between factor slices)
 from .graph import Graph, coalesce_device, creat_adj  # noqa: F401  (creat_adj re-exported)
 
@@ -105,33 +105,33 @@ def loss_kind_id(loss_func):
     return _lib.LOSS_LOGSIGMOID if loss_func == "logsigmoid" else _lib.LOSS_SOFTPLUS
 
 
-class _RankingLoss(torch.autograd.Function):
-    """Multi-negative ranking loss on tables + a [B, 2 + K] tuple batch: the (2 + K) B rows are gathered, the compact kernels
-    (rowops.rank_fwd / rank_bwd) run on them and the compact gradients are folded back onto the tables.
-    Returns a 2-vector: [mul_loss, l2reg_loss (unweighted)]."""
+class _GatheredRowsLoss(torch.autograd.Function):
+    """A loss stage (loss_stage.py) on tables + an id batch: the batch's rows are gathered, the stage's compact kernels run on
+    them and the compact gradients are folded back onto the tables.
+    Returns [mul_loss, l2reg_loss (unweighted), *stage.extra]; only the first two carry a gradient."""
 
     @staticmethod
-    def forward(ctx, U, I, Ureg, Ireg, tuples, loss_kind, temperature, plans):
+    def forward(ctx, U, I, Ureg, Ireg, batch, stage, plans):
+        name = stage.name
         for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2):
-                raise _lib.TagrecError(f"ranking_loss: {nm} must be a 2-d float32 GPU tensor")
-        tuples = _lib.require_gpu_tensor(tuples.contiguous(), torch.int64, "ranking_loss tuples")
-        if tuples.dim() != 2 or tuples.shape[1] < 3:
-            raise _lib.TagrecError(f"ranking_loss: tuples {tuple(tuples.shape)} must be [B, 2 + K]")
-        urows, irows = tuples[:, 0].contiguous(), tuples[:, 1:].t().reshape(-1)       # item j of tuple b at slot j B + b
+                raise _lib.TagrecError(f"{name}: {nm} must be a 2-d float32 GPU tensor")
+        batch = _lib.require_gpu_tensor(batch.contiguous(), torch.int64, f"{name} {stage.batch_word}")
+        stage.check(name, batch)
+        urows, irows = stage.ids(batch)
         Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
         has_reg = Ureg is not None
         same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
         Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
-        out, coef = rowops.rank_fwd(Ub, Ib, Urb, Irb, loss_kind, temperature)
-        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows, coef)
-        ctx.has_reg, ctx.same, ctx.plans = has_reg, same, plans
+        res = stage.fwd(batch, Ub, Ib, Urb, Irb)
+        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows)
+        ctx.stage, ctx.has_reg, ctx.same, ctx.plans = stage, has_reg, same, plans
         ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
-        return out
+        return res if stage.extra is None else torch.cat([res, stage.extra])
 
     @staticmethod
     def backward(ctx, g):
-        Ub, Ib, Urb, Irb, urows, irows, coef = ctx.saved_tensors
+        Ub, Ib, Urb, Irb, urows, irows = ctx.saved_tensors
         pu, pi = ctx.plans if ctx.plans is not None else (None, None)
         dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
         if ctx.has_reg and ctx.same:
@@ -140,15 +140,25 @@ class _RankingLoss(torch.autograd.Function):
             dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
         else:
             Urb = Irb = dUrb = dIrb = None
-        rowops.rank_bwd(Ub, Ib, Urb, Irb, coef, g, dUb, dIb, dUrb, dIrb)
+        ctx.stage.bwd(Ub, Ib, Urb, Irb, g, dUb, dIb, dUrb, dIrb)
 
         def fold(shape, rows, src, plan):
             return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
 
         dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
         if ctx.has_reg and not ctx.same:
-            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
-        return dU, dI, None, None, None, None, None, None
+            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None
+        return dU, dI, None, None, None, None, None
+
+
+def stage_loss(stage, U, I, Ureg, Ireg, batch, plans=None):
+    """[mul_loss, l2reg_loss (unweighted), *stage.extra] of `batch` against user / item tables under a loss stage: what the
+    fused steps' autograd nodes return, operator by operator.  The triplet stage gathers inside its kernels (`_TripletLoss`)."""
+    if isinstance(stage, S.Triplet):
+        if Ureg is not None and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr():
+            Ureg, Ireg = U, I          # reg on the same rows: one gradient buffer
+        return _TripletLoss.apply(U, I, Ureg, Ireg, batch, stage.loss_kind)
+    return _GatheredRowsLoss.apply(U, I, Ureg, Ireg, batch, stage, plans)
 
 
 def rank_route(model, batch, n_negatives, loss_func, temperature):
@@ -175,71 +185,14 @@ def ranking_loss(U, I, Ureg, Ireg, tuples, loss_func, temperature=1.0, plans=Non
     l2reg_loss = 0.5 (|u|^2 + |p|^2 + sum_k |n_k|^2) / B on the rows of Ureg / Ireg (None: 0).
     plans (`ranking_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
     instead of by `index_add_`."""
-    out = _RankingLoss.apply(U, I, Ureg, Ireg, tuples, loss_kind_id(loss_func), float(temperature), plans)
+    out = stage_loss(S.Rank(loss_kind_id(loss_func), float(temperature)), U, I, Ureg, Ireg, tuples, plans)
     return out[0], out[1]
-
-
-class _InBatchLoss(torch.autograd.Function):
-    """In-batch softmax loss on tables + a [B, 2] pair batch: the 2 B rows are gathered, the fused B x B kernels
-    (rowops.inbatch_fwd / inbatch_bwd) run on them and the compact gradients are folded back onto the tables.
-    Returns a 2-vector: [mul_loss, l2reg_loss (unweighted)]."""
-
-    @staticmethod
-    def forward(ctx, U, I, Ureg, Ireg, pairs, temperature, item_logq, plans):
-        for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
-            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2):
-                raise _lib.TagrecError(f"in_batch_loss: {nm} must be a 2-d float32 GPU tensor")
-        pairs = _lib.require_gpu_tensor(pairs.contiguous(), torch.int64, "in_batch_loss pairs")
-        if pairs.dim() != 2 or pairs.shape[1] != 2:
-            raise _lib.TagrecError(f"in_batch_loss: pairs {tuple(pairs.shape)} must be [B, 2] = (user, positive)")
-        urows, irows = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
-        bias = None if item_logq is None else item_logq.index_select(0, irows)
-        Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
-        has_reg = Ureg is not None
-        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
-        Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
-        out, lse = rowops.inbatch_fwd(Ub, Ib, Urb, Irb, temperature, urows, irows, bias)
-        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows, lse,
-                              bias if bias is not None else U.new_empty(0))
-        ctx.has_reg, ctx.same, ctx.plans, ctx.tau, ctx.has_bias = has_reg, same, plans, temperature, bias is not None
-        ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        Ub, Ib, Urb, Irb, urows, irows, lse, bias = ctx.saved_tensors
-        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
-        dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
-        if ctx.has_reg and ctx.same:
-            Urb, Irb, dUrb, dIrb = Ub, Ib, dUb, dIb        # reg on the same rows: one gradient buffer
-        elif ctx.has_reg:
-            dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
-        else:
-            Urb = Irb = dUrb = dIrb = None
-        rowops.inbatch_bwd(Ub, Ib, Urb, Irb, ctx.tau, lse, g, dUb, dIb, dUrb, dIrb, urows, irows, bias if ctx.has_bias else None)
-
-        def fold(shape, rows, src, plan):
-            return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
-
-        dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
-        if ctx.has_reg and not ctx.same:
-            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
-        return dU, dI, None, None, None, None, None, None
 
 
 class InBatchRoute(NamedTuple):
     """What a fused step is handed in place of `rank_route`'s (K, temperature) when the model has negatives="in_batch"."""
     temperature: float
     item_logq: Optional[torch.Tensor]      # [n_item] logQ table, or None: no column bias
-
-
-class InBatchState(NamedTuple):
-    """What the in-batch loss stage of a fused step keeps between its forward and its backward."""
-    temperature: float
-    uid: torch.Tensor                      # [B] the mask ids: the two columns of the pair batch
-    iid: torch.Tensor
-    bias: Optional[torch.Tensor]           # [B] item_logq of the batch's items, or None
-    lse: torch.Tensor                      # [B] row log-sum-exp written by the forward
 
 
 def in_batch_route(model, batch, temperature, item_logq=None):
@@ -249,19 +202,6 @@ def in_batch_route(model, batch, temperature, item_logq=None):
         raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit negatives=\"in_batch\" "
                                "(expected [B, 2] = user, positive; the negatives are the other positives of the batch)")
     return InBatchRoute(float(temperature), item_logq)
-
-
-def in_batch_stage_fwd(route, pairs, Ub, Ib, Ureg, Ireg):
-    """The loss stage of a fused step on its gathered rows (users, then positives) -> (res, InBatchState)."""
-    uid, iid = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
-    bias = None if route.item_logq is None else route.item_logq.index_select(0, iid)
-    res, lse = rowops.inbatch_fwd(Ub, Ib, Ureg, Ireg, route.temperature, uid, iid, bias)
-    return res, InBatchState(route.temperature, uid, iid, bias, lse)
-
-
-def in_batch_stage_bwd(state, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg):
-    """Its backward: one launch stores the gradient rows of both loss parts (`rowops.inbatch_bwd`)."""
-    rowops.inbatch_bwd(Ub, Ib, Ureg, Ireg, state.temperature, state.lse, g, dUb, dIb, dUreg, dIreg, state.uid, state.iid, state.bias)
 
 
 def in_batch_plans(pairs, n_user, n_item, width=256):
@@ -291,7 +231,7 @@ def in_batch_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, item_logq=None, plan
     correction); l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg (None: 0).  The B x B scores are never stored.
     plans (`in_batch_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
     instead of by `index_add_`."""
-    out = _InBatchLoss.apply(U, I, Ureg, Ireg, pairs, float(temperature), item_logq, plans)
+    out = stage_loss(S.InBatch(float(temperature), item_logq), U, I, Ureg, Ireg, pairs, plans)
     return out[0], out[1]
 
 
@@ -303,69 +243,20 @@ class AuRoute(NamedTuple):
 
 def au_route(model, batch, t=2.0, gamma=1.0):
     """A DirectAU model takes [B, 2] = (user, positive) batches; any other width is refused.  -> the `AuRoute` of its step."""
-    if batch.dim() != 2 or batch.shape[1] != 2:
-        raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit the alignment / uniformity loss "
-                               "(expected [B, 2] = user, positive; nothing is sampled)")
-    if batch.shape[0] < 2:
-        raise _lib.TagrecError(f"{model}: a batch of one pair (B = 1) has no other pair to be uniform against")
-    return AuRoute(float(t), float(gamma))
+    route = AuRoute(float(t), float(gamma))
+    S.Au(*route).check(model, batch)
+    return route
 
 
-def au_stage_fwd(route, pairs, Ub, Ib, Ureg, Ireg):
-    """The DirectAU loss stage of a fused step on its gathered rows (users, then positives) -> (res, state); state.parts is
-    the device tensor [align, unif_u, unif_i]."""
-    res, _, state = rowops.directau_fwd(Ub, Ib, Ureg, Ireg, route.t, route.gamma)
-    return res, state
-
-
-def au_stage_bwd(state, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg):
-    """Its backward: one launch stores the gradient rows of both loss parts (`rowops.directau_bwd`)."""
-    rowops.directau_bwd(Ub, Ib, Ureg, Ireg, state, g, dUb, dIb, dUreg, dIreg)
-
-
-class _AlignUniformLoss(torch.autograd.Function):
-    """DirectAU loss on tables + a [B, 2] pair batch: the 2 B rows are gathered, the fused kernels (rowops.directau_fwd /
-    directau_bwd) run on them and the compact gradients are folded back onto the tables.
-    Returns a 5-vector: [mul_loss, l2reg_loss (unweighted), align, unif_u, unif_i]; only the first two carry a gradient."""
-
-    @staticmethod
-    def forward(ctx, U, I, Ureg, Ireg, pairs, t, gamma, plans):
-        for x, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
-            if x is not None and (not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2):
-                raise _lib.TagrecError(f"align_uniform_loss: {nm} must be a 2-d float32 GPU tensor")
-        pairs = _lib.require_gpu_tensor(pairs.contiguous(), torch.int64, "align_uniform_loss pairs")
-        au_route("align_uniform_loss", pairs)
-        urows, irows = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
-        Ub, Ib = U.index_select(0, urows), I.index_select(0, irows)
-        has_reg = Ureg is not None
-        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
-        Urb, Irb = (Ub, Ib) if same else ((Ureg.index_select(0, urows), Ireg.index_select(0, irows)) if has_reg else (None, None))
-        res, parts, ctx.state = rowops.directau_fwd(Ub, Ib, Urb, Irb, t, gamma)
-        ctx.save_for_backward(Ub, Ib, Urb if has_reg else U.new_empty(0), Irb if has_reg else U.new_empty(0), urows, irows)
-        ctx.has_reg, ctx.same, ctx.plans = has_reg, same, plans
-        ctx.shapes = (U.shape, I.shape, Ureg.shape if has_reg else None, Ireg.shape if has_reg else None)
-        return torch.cat([res, parts])
-
-    @staticmethod
-    def backward(ctx, g):
-        Ub, Ib, Urb, Irb, urows, irows = ctx.saved_tensors
-        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
-        dUb, dIb = torch.empty_like(Ub), torch.empty_like(Ib)
-        if ctx.has_reg and ctx.same:
-            Urb, Irb, dUrb, dIrb = Ub, Ib, dUb, dIb        # reg on the same rows: one gradient buffer
-        elif ctx.has_reg:
-            dUrb, dIrb = torch.empty_like(Urb), torch.empty_like(Irb)
-        else:
-            Urb = Irb = dUrb = dIrb = None
-        rowops.directau_bwd(Ub, Ib, Urb, Irb, ctx.state, g[:2], dUb, dIb, dUrb, dIrb)
-
-        def fold(shape, rows, src, plan):
-            return rowops.fold_rows(torch.zeros(shape, dtype=torch.float32, device=src.device), rows, src, plan)
-
-        dU, dI = fold(ctx.shapes[0], urows, dUb, pu), fold(ctx.shapes[1], irows, dIb, pi)
-        if ctx.has_reg and not ctx.same:
-            return dU, dI, fold(ctx.shapes[2], urows, dUrb, pu), fold(ctx.shapes[3], irows, dIrb, pi), None, None, None, None
-        return dU, dI, None, None, None, None, None, None
+def stage_for(route, loss_kind):
+    """The loss stage (loss_stage.py) of a step that was handed `route` -- the one place that tells the route values apart."""
+    if route is None:
+        return S.Triplet(loss_kind)
+    if isinstance(route, InBatchRoute):
+        return S.InBatch(*route)
+    if isinstance(route, AuRoute):
+        return S.Au(*route)
+    return S.Rank(loss_kind, route[1])
 
 
 def align_uniform_loss(U, I, Ureg, Ireg, pairs, t=2.0, gamma=1.0, plans=None, parts_out=None):
@@ -375,7 +266,7 @@ def align_uniform_loss(U, I, Ureg, Ireg, pairs, t=2.0, gamma=1.0, plans=None, pa
     (None: 0).  The B x B potentials are never stored.  0 < t <= 20, B >= 2.
     plans (`in_batch_plans`): the compact gradients are folded onto the tables in a fixed order (the same bits every run)
     instead of by `index_add_`.  parts_out (a list): receives the detached device tensor [align, unif_u, unif_i]."""
-    out = _AlignUniformLoss.apply(U, I, Ureg, Ireg, pairs, float(t), float(gamma), plans)
+    out = stage_loss(S.Au(float(t), float(gamma)), U, I, Ureg, Ireg, pairs, plans)
     if parts_out is not None:
         parts_out.append(out[2:].detach())
     return out[0], out[1]
@@ -383,9 +274,7 @@ def align_uniform_loss(U, I, Ureg, Ireg, pairs, t=2.0, gamma=1.0, plans=None, pa
 
 def triplet_loss(U, I, Ureg, Ireg, trip, loss_func):
     """(mul_loss, l2reg_loss) of a [B,3] triplet batch against user/item tables."""
-    if Ureg is not None and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr():
-        Ureg, Ireg = U, I          # reg on the same rows: one gradient buffer
-    out = _TripletLoss.apply(U, I, Ureg, Ireg, trip, loss_kind_id(loss_func))
+    out = stage_loss(S.Triplet(loss_kind_id(loss_func)), U, I, Ureg, Ireg, trip)
     return out[0], out[1]
 
 

@@ -19,6 +19,7 @@ from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_bu
 from .base import layer_seed as _layer_seed
 from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
 from .graph import EdgeDropView, Graph, creat_adj
+from .loss_stage import Triplet
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
@@ -251,159 +252,80 @@ class _Propagate(torch.autograd.Function):
 
 
 class _PropagateBprLoss(torch.autograd.Function):
-    """table -> [mul_loss, l2reg_loss(ego rows)] in one autograd node."""
+    """table -> [mul_loss, l2reg_loss(ego rows), *stage.extra] in one autograd node; stage: the loss stage (loss_stage.py)."""
 
     @staticmethod
-    def forward(ctx, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active, drops=None, seed=0, restrict=True,
-                fused_opt=None, ws=None, deterministic=False, rank=None):
+    def forward(ctx, table, graph, n_layer, n_user, n_item, batch, stage, reg_active, drops=None, seed=0, restrict=True,
+                fused_opt=None, ws=None, deterministic=False):
         x0 = table.detach()
-        # rank = (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*);
-        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*);
-        # an H.AuRoute: a [B, 2] pair batch under the alignment / uniformity loss (rowops.directau_*)
-        if rank is not None:
-            return _PropagateBprLoss._forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, trip, loss_kind, reg_active,
-                                                   drops, seed, restrict, fused_opt, ws, deterministic, rank)
-        ctx.rank = None
-        ctx.fused = (table, fused_opt) if fused_opt is not None else None
+        n, D = x0.shape
         ctx.ws, ctx.token = None, _Token()
         if ws is not None and ws.acquire(ctx.token):
             ctx.ws = ws
-        B, D = trip.shape[0], x0.shape[1]
-        n = x0.shape[0]
-        ctx.n_user, ctx.n_item, ctx.reg_active, ctx.trip, ctx.graph = n_user, n_item, reg_active, trip, graph
-        # the loss reads `out` at the batch rows only: users, and items offset by n_user
-        rows = rowops.batch_rows(trip, n_user) if (restrict or deterministic) else None
+        # compact: the loss reads `out` at the batch rows only, and the top layers run on them alone (a batch that touches
+        # most rows gains nothing); on_tables: the triplet kernels gather from the full tables themselves
+        compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
+                       and batch.numel() * 16 <= n)
+        on_tables = not compact and isinstance(stage, Triplet)
+        rows = stage.rows(batch, n_user) if (restrict or deterministic or not on_tables) else None
         # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
-        ctx.plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
-        ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
-                           and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
-        if ctx.compact:
-            out_b, ctx.state, ego_b = restricted_forward(graph, x0, n_layer, rows, ctx.ws, want_ego=True)
-            ctrip = rowops.compact_triplets(B, x0.device)
-            res, ctx.coef = rowops.bpr_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctrip, loss_kind)
-            ctx.rows, ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.shape = rows, out_b, ego_b, ctrip, x0.shape
-            return res
-        ctx.masks = {}
-        out, raws, invs = propagate_forward(graph, x0, n_layer, drops, seed, rows if restrict else None, ctx.masks)
-        ctx.drops, ctx.seed = drops, seed
-        U, I = out[:n_user], out[n_user:n_user + n_item]
-        Ue, Ie = x0[:n_user], x0[n_user:n_user + n_item]
-        res, ctx.coef = rowops.bpr_fwd(U, I, Ue, Ie, trip, loss_kind)
-        ctx.raws, ctx.invs = raws, invs
-        ctx.out, ctx.x0 = out, x0
-        return res
-
-    @staticmethod
-    def _forward_rank(ctx, x0, table, graph, n_layer, n_user, n_item, tuples, loss_kind, reg_active, drops, seed, restrict,
-                      fused_opt, ws, deterministic, rank):
-        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd` / `rowops.directau_fwd`: only the row list changes,
-        T = (2 + K) B (pair batches: K = 0);
-        everything around it is the triplet step's.  The all-rows path gathers the T rows of `out` (the kernels take compact
-        rows only)."""
-        ctx.rank = rank
-        ctx.fused = (table, fused_opt) if fused_opt is not None else None
-        ctx.ws, ctx.token = None, _Token()
-        if ws is not None and ws.acquire(ctx.token):
-            ctx.ws = ws
-        B, (n, D) = tuples.shape[0], x0.shape
-        ctx.reg_active, ctx.graph, ctx.B, ctx.shape = reg_active, graph, B, x0.shape
-        rows = ctx.rows = rowops.tuple_rows(tuples, n_user)
-        ctx.plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
-        ctx.compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
-                           and rows.numel() * 16 <= n)              # a batch that touches most rows gains nothing
-        if ctx.compact:
+        plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
+        B = batch.shape[0]
+        if compact:
             out_b, ctx.state, ego_b = restricted_forward(graph, x0, n_layer, rows, ctx.ws, want_ego=True)
         else:
             ctx.masks = {}
             out, ctx.raws, ctx.invs = propagate_forward(graph, x0, n_layer, drops, seed, rows if restrict else None, ctx.masks)
             ctx.drops, ctx.seed = drops, seed
-            out_b = out.index_select(0, rows)
-            ego_b = x0.index_select(0, rows)
-        ctx.in_batch = ctx.au = None
-        if isinstance(rank, H.InBatchRoute):
-            res, ctx.in_batch = H.in_batch_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
-        elif isinstance(rank, H.AuRoute):
-            res, ctx.au = H.au_stage_fwd(rank, tuples, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
-            res = torch.cat([res, ctx.au.parts])            # [mul_loss, l2reg, align, unif_u, unif_i]: the last three carry no gradient
+        if on_tables:
+            res = stage.fwd_on_tables(batch, out, x0, n_user, n_item)
+            ctx.saved = (out, x0)
         else:
-            res, ctx.coef = rowops.rank_fwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], loss_kind, rank[1])
-        ctx.out_b, ctx.ego_b = out_b, ego_b
-        return res
-
-    @staticmethod
-    def _backward_rank(ctx, g):
-        out_b, ego_b, rows, B = ctx.out_b, ctx.ego_b, ctx.rows, ctx.B
-        d_b = torch.empty_like(out_b)                                      # d / d out_b: every row is stored by the kernel
-        d_e = None
-        if ctx.in_batch is not None or ctx.au is not None:  # one launch stores both parts (the L2 rows are folded after the hop, below)
-            d_e = torch.empty_like(ego_b) if ctx.reg_active else None
-            reg = (ego_b[:B], ego_b[B:], d_e[:B], d_e[B:]) if ctx.reg_active else (None,) * 4
-            if ctx.au is not None:
-                H.au_stage_bwd(ctx.au, out_b[:B], out_b[B:], reg[0], reg[1], g[:2], d_b[:B], d_b[B:], reg[2], reg[3])
-            else:
-                H.in_batch_stage_bwd(ctx.in_batch, out_b[:B], out_b[B:], reg[0], reg[1], g, d_b[:B], d_b[B:], reg[2], reg[3])
-            ctx.in_batch = ctx.au = None
-        else:
-            rowops.rank_bwd(out_b[:B], out_b[B:], None, None, ctx.coef, g, d_b[:B], d_b[B:], None, None)
-        if ctx.compact:
-            fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
-            g0 = restricted_backward(ctx.graph.transpose(), rows, d_b, ctx.state, ctx.shape, fused, ctx.ws, ctx.plan)
-            ctx.state = None
-        else:
-            d_out = rowops.fold_rows(torch.zeros(ctx.shape, dtype=torch.float32, device=out_b.device), rows, d_b, ctx.plan)
-            fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active and len(ctx.raws) >= 1) else None
-            g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
-            ctx.raws = ctx.invs = None
-        if ctx.reg_active:                                                 # L2 term on the ego rows, after the hop has written g0
-            if d_e is None:
-                d_e = torch.empty_like(ego_b)
-                rowops.rank_bwd(out_b[:B], out_b[B:], ego_b[:B], ego_b[B:], ctx.coef, g, None, None, d_e[:B], d_e[B:], "rank_bwd(reg)")
-            rowops.fold_rows(g0, rows, d_e, ctx.plan)
-        ctx.out_b = ctx.ego_b = None
-        if ctx.ws is not None:
-            ctx.ws.release(ctx.token)
-        return (g0,) + (None,) * 14
+            if not compact:                  # the kernels take gathered rows only
+                out_b, ego_b = out.index_select(0, rows), x0.index_select(0, rows)
+            res = stage.fwd(batch, out_b[:B], out_b[B:], ego_b[:B], ego_b[B:])
+            ctx.saved = (out_b, ego_b)
+        # (table, optimizer): Adam in the epilogue of the backward pass's last hop -- which the L2 term would arrive too late for
+        ctx.fused = (table, fused_opt) if (fused_opt is not None and not reg_active and n_layer >= 1) else None
+        ctx.graph, ctx.stage, ctx.rows, ctx.plan, ctx.B, ctx.shape = graph, stage, rows, plan, B, x0.shape
+        ctx.compact, ctx.on_tables, ctx.reg_active = compact, on_tables, reg_active
+        return res if stage.extra is None else torch.cat([res, stage.extra])      # the extra entries carry no gradient
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.rank is not None:
-            return _PropagateBprLoss._backward_rank(ctx, g)
-        if ctx.compact:
-            out_b, ego_b, ctrip, rows = ctx.out_b, ctx.ego_b, ctx.ctrip, ctx.rows
-            B, D = ctrip.shape[0], out_b.shape[1]
-            d_b = torch.zeros(2, 3 * B, D, dtype=torch.float32, device=out_b.device)   # d / d out_b, d / d ego_b
-            Ue, Ie, dUe, dIe = (ego_b[:B], ego_b[B:], d_b[1][:B], d_b[1][B:]) if ctx.reg_active else (None,) * 4
-            rowops.bpr_bwd(out_b[:B], out_b[B:], Ue, Ie, ctrip, ctx.coef, g, d_b[0][:B], d_b[0][B:], dUe, dIe)
-            fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active) else None
-            g0 = restricted_backward(ctx.graph.transpose(), rows, d_b[0], ctx.state, ctx.shape, fused, ctx.ws, ctx.plan)
-            if ctx.reg_active and ctx.plan is not None:
-                rowops.scatter_rows_ordered(g0, ctx.plan, d_b[1], True)   # L2 term on the ego rows
-            elif ctx.reg_active:
-                g0.index_add_(0, rows, d_b[1])                            # L2 term on the ego rows
-            ctx.state = ctx.out_b = None
-            if ctx.ws is not None:
-                ctx.ws.release(ctx.token)
-            return (g0,) + (None,) * 14
-        out, x0, trip = ctx.out, ctx.x0, ctx.trip
-        nu, ni = ctx.n_user, ctx.n_item
-        d_out = torch.zeros_like(out)
-        U, I = out[:nu], out[nu:nu + ni]
-        if ctx.plan is not None:
-            rowops.bpr_bwd_ordered(out, None, trip, ctx.coef, g, d_out, None, ctx.plan)
+        stage, rows, plan, B, reg = ctx.stage, ctx.rows, ctx.plan, ctx.B, ctx.reg_active
+        graph_t = ctx.graph.transpose()
+        if ctx.on_tables:
+            out, x0 = ctx.saved
+            d_out = torch.zeros_like(out)
+            stage.bwd_on_tables(out, None, g, d_out, None, plan)
         else:
-            rowops.bpr_bwd(U, I, None, None, trip, ctx.coef, g, d_out[:nu], d_out[nu:nu + ni], None, None)
-        fused = ctx.fused if (ctx.fused is not None and not ctx.reg_active and len(ctx.raws) >= 1) else None
-        g0 = propagate_backward(ctx.graph.transpose(), d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, fused)
+            out_b, ego_b = ctx.saved
+            # d / d out_b, d / d ego_b
+            d_b, d_e = (torch.zeros if stage.grads_zeroed else torch.empty)(2, *out_b.shape, dtype=torch.float32, device=out_b.device)
+            U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
+            Ue, Ie, dUe, dIe = (ego_b[:B], ego_b[B:], d_e[:B], d_e[B:]) if reg else (None,) * 4
+            if reg and stage.reg_apart:      # the L2 rows get a launch of their own, below
+                stage.bwd(U, I, None, None, g, dU, dI, None, None)
+            else:
+                stage.bwd(U, I, Ue, Ie, g, dU, dI, dUe, dIe)
+        if ctx.compact:
+            g0 = restricted_backward(graph_t, rows, d_b, ctx.state, ctx.shape, ctx.fused, ctx.ws, plan)
+        else:
+            if not ctx.on_tables:
+                d_out = rowops.fold_rows(torch.zeros(ctx.shape, dtype=torch.float32, device=d_b.device), rows, d_b, plan)
+            g0 = propagate_backward(graph_t, d_out, ctx.raws, ctx.invs, ctx.drops, ctx.seed, ctx.masks, ctx.fused)
         # L2 term on the ego rows: added after the propagation hop has written g0
-        if ctx.reg_active and ctx.plan is not None:
-            rowops.bpr_bwd_ordered(out, x0, trip, ctx.coef, g, None, g0, ctx.plan, True, "bpr_bwd(reg)")
-        elif ctx.reg_active:
-            Ue, Ie = x0[:nu], x0[nu:nu + ni]
-            rowops.bpr_bwd(U, I, Ue, Ie, trip, ctx.coef, g, None, None, g0[:nu], g0[nu:nu + ni], "bpr_bwd(reg)")
-        ctx.raws = ctx.invs = ctx.out = None
+        if reg and ctx.on_tables:
+            stage.bwd_on_tables(out, x0, g, None, g0, plan, "reg")
+        elif reg:
+            if stage.reg_apart:
+                stage.bwd(U, I, Ue, Ie, g, None, None, dUe, dIe, "reg")
+            rowops.fold_rows(g0, rows, d_e, plan)
+        ctx.state = ctx.raws = ctx.invs = ctx.saved = None
         if ctx.ws is not None:
             ctx.ws.release(ctx.token)
-        return (g0,) + (None,) * 14
+        return (g0,) + (None,) * 13
 
 
 class LightGCN(FusedStepModel):
@@ -495,32 +417,19 @@ class LightGCN(FusedStepModel):
     def loss(self, batch_data):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
-        rank = self._route(batch_data)
+        stage = H.stage_for(self._route(batch_data), H.loss_kind_id(self.loss_func))
         if self._fused_ok():
             graph = self._graph()                       # (first: kernel-mode edge dropout refuses a capture before any launch)
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
-            res = _PropagateBprLoss.apply(self.table, graph, self.num_layer, nu, ni, batch_data,
-                                          H.loss_kind_id(self.loss_func), self.reg != 0, drops, seed, self.restrict_forward,
-                                          fused, self.step_ws if (self.training and torch.is_grad_enabled()) else None,
-                                          self.deterministic, rank)
-            if isinstance(rank, H.AuRoute):
-                self.last_au_parts = res[2:].detach()
-            return res[0], self.reg * res[1]
-        if self.deterministic:
+            res = _PropagateBprLoss.apply(self.table, graph, self.num_layer, nu, ni, batch_data, stage, self.reg != 0, drops, seed,
+                                          self.restrict_forward, fused,
+                                          self.step_ws if (self.training and torch.is_grad_enabled()) else None, self.deterministic)
+        elif self.deterministic:
             raise _lib.TagrecError("LightGCN: deterministic=True covers the fused step only (no row folds: split_adj_k == 1)")
-        all_users, all_items = self.forward()[:2]
-        ego = self.embed
-        if isinstance(rank, H.AuRoute):
-            parts = []
-            loss, reg_loss = H.align_uniform_loss(all_users, all_items, ego[0], ego[1], batch_data, rank.t, rank.gamma, parts_out=parts)
-            self.last_au_parts = parts[0]
-            return loss, self.reg * reg_loss
-        if isinstance(rank, H.InBatchRoute):
-            loss, reg_loss = H.in_batch_loss(all_users, all_items, ego[0], ego[1], batch_data, rank.temperature, rank.item_logq)
-            return loss, self.reg * reg_loss
-        if rank is not None:
-            loss, reg_loss = H.ranking_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func, rank[1])
-            return loss, self.reg * reg_loss
-        loss, reg_loss = H.triplet_loss(all_users, all_items, ego[0], ego[1], batch_data, self.loss_func)
-        return loss, self.reg * reg_loss
+        else:
+            all_users, all_items = self.forward()[:2]
+            res = H.stage_loss(stage, all_users, all_items, *self.embed[:2], batch_data)
+        if stage.extra is not None:
+            self.last_au_parts = res[2:].detach()
+        return res[0], self.reg * res[1]

@@ -1,0 +1,142 @@
+"""The loss stage of a LightGCN / NGCF step and of help.py's table losses: the one thing that varies between the objectives.
+
+A stage is made per step (`help.stage_for(route, loss_kind)`, or directly by help.py's loss functions), runs one kernel pair of
+rowops.py on GATHERED rows -- Ub [B, D] the batch's users, Ib [T - B, D] its items in slot order -- and keeps what its backward
+needs (coef / lse / AuState) on itself:
+
+    stage.rows(batch, n_user)              -> int64 node ids [T] of the [user | item] table, in the slot order of the kernels
+    stage.ids(batch)                       -> (user ids [B], item ids [T - B]) of the same slots, for separate tables
+    stage.check(name, batch)               refuses a batch of another shape in `name`'s words (the table losses)
+    stage.fwd(batch, Ub, Ib, Ureg, Ireg)   -> res = [mul_loss, l2reg_loss (unweighted)]; Ureg / Ireg: the L2 rows, or None
+    stage.bwd(Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None)
+                                           the gradient rows of both parts (g = their upstream gradients); dUb = dIb = None: the
+                                           L2 part only, Ureg = Ireg = None: no L2 part, dUreg is dUb: one buffer takes the sum
+    stage.grads_zeroed                     True: the backward scatter-adds into caller-ZEROED rows; False: it STORES every row
+    stage.reg_apart                        True: a step whose L2 rows are not its loss rows launches the backward once per part
+    stage.extra                            None, or a device tensor the forward leaves to be appended to `res` (no gradient)
+
+`Triplet` has a second form, `fwd_on_tables` / `bwd_on_tables`, for the all-rows step: its kernels take the real triplets and
+gather from the full tables themselves, so that step has no gathered rows at all.
+"""
+from . import _lib, rowops
+
+
+class _Stage:
+    name = batch_word = None                 # the table loss of this stage in help.py and what it calls its batch
+    grads_zeroed = reg_apart = False
+    extra = None
+    _ids = None
+
+    def rows(self, batch, n_user):
+        return rowops.tuple_rows(batch, n_user)
+
+    def ids(self, batch):
+        if self._ids is None:                # item j of tuple b at slot j B + b
+            self._ids = (batch[:, 0].contiguous(), batch[:, 1:].t().contiguous().view(-1))
+        return self._ids
+
+    @staticmethod
+    def _what(kernel, what):
+        return () if what is None else (f"{kernel}({what})",)
+
+
+class Triplet(_Stage):
+    """[B, 3] = (user, positive, negative): `rowops.bpr_fwd` / `bpr_bwd` on `compact_triplets` of the gathered rows."""
+    grads_zeroed = True
+
+    def __init__(self, loss_kind):
+        self.loss_kind = loss_kind
+
+    def rows(self, batch, n_user):
+        return rowops.batch_rows(batch, n_user)
+
+    def fwd(self, batch, Ub, Ib, Ureg, Ireg):
+        self.trip = rowops.compact_triplets(batch.shape[0], batch.device)
+        res, self.coef = rowops.bpr_fwd(Ub, Ib, Ureg, Ireg, self.trip, self.loss_kind)
+        return res
+
+    def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
+        rowops.bpr_bwd(Ub, Ib, Ureg, Ireg, self.trip, self.coef, g, dUb, dIb, dUreg, dIreg, *self._what("bpr_bwd", what))
+
+    def fwd_on_tables(self, batch, out, ego, n_user, n_item):
+        """The stage on the full [user | item] tables `out` (and `ego`: the L2 part's): the gather is the kernel's."""
+        self.trip = batch
+        self._cut = lambda t: (None, None) if t is None else (t[:n_user], t[n_user:n_user + n_item])
+        res, self.coef = rowops.bpr_fwd(*self._cut(out), *self._cut(ego), batch, self.loss_kind)
+        return res
+
+    def bwd_on_tables(self, out, ego, g, d_out, d_ego, plan=None, what=None):
+        """Scatter-adds into d_out / d_ego (ego None: no L2 part; d_out None: the L2 part only, added to what d_ego holds).
+        plan (the `row_list_plan` of `rows`): `rowops.bpr_bwd_ordered`, no float atomics on repeated ids."""
+        if plan is not None:
+            rowops.bpr_bwd_ordered(out, ego, self.trip, self.coef, g, d_out, d_ego, plan, d_out is None,
+                                   *self._what("bpr_bwd", what))
+        else:
+            rowops.bpr_bwd(*self._cut(out), *self._cut(ego), self.trip, self.coef, g, *self._cut(d_out), *self._cut(d_ego),
+                           *self._what("bpr_bwd", what))
+
+
+class Rank(_Stage):
+    """[B, 2 + K] = (user, positive, K negatives): the multi-negative kernels `rowops.rank_fwd` / `rank_bwd`."""
+    name, batch_word = "ranking_loss", "tuples"
+    reg_apart = True         # (one launch that stores both parts would do; the steps have always launched two)
+
+    def __init__(self, loss_kind, temperature):
+        self.loss_kind, self.temperature = loss_kind, temperature
+
+    def check(self, name, batch):
+        if batch.dim() != 2 or batch.shape[1] < 3:
+            raise _lib.TagrecError(f"{name}: tuples {tuple(batch.shape)} must be [B, 2 + K]")
+
+    def fwd(self, batch, Ub, Ib, Ureg, Ireg):
+        res, self.coef = rowops.rank_fwd(Ub, Ib, Ureg, Ireg, self.loss_kind, self.temperature)
+        return res
+
+    def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
+        rowops.rank_bwd(Ub, Ib, Ureg, Ireg, self.coef, g, dUb, dIb, dUreg, dIreg, *self._what("rank_bwd", what))
+
+
+class InBatch(_Stage):
+    """[B, 2] = (user, positive), the other positives are the negatives: the fused B x B kernels `rowops.inbatch_fwd` /
+    `inbatch_bwd` with the batch's ids as masks and item_logq ([n_item], or None) as the column bias."""
+    name, batch_word = "in_batch_loss", "pairs"
+
+    def __init__(self, temperature, item_logq=None):
+        self.temperature, self.item_logq = temperature, item_logq
+
+    def check(self, name, batch):
+        if batch.dim() != 2 or batch.shape[1] != 2:
+            raise _lib.TagrecError(f"{name}: pairs {tuple(batch.shape)} must be [B, 2] = (user, positive)")
+
+    def fwd(self, batch, Ub, Ib, Ureg, Ireg):
+        uid, iid = self.ids(batch)
+        self.bias = None if self.item_logq is None else self.item_logq.index_select(0, iid)
+        res, self.lse = rowops.inbatch_fwd(Ub, Ib, Ureg, Ireg, self.temperature, uid, iid, self.bias)
+        return res
+
+    def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
+        rowops.inbatch_bwd(Ub, Ib, Ureg, Ireg, self.temperature, self.lse, g, dUb, dIb, dUreg, dIreg, *self._ids, self.bias,
+                           *self._what("inbatch_bwd", what))
+
+
+class Au(_Stage):
+    """[B, 2] = (user, positive) under the alignment / uniformity loss: `rowops.directau_fwd` / `directau_bwd`.
+    extra = [align, unif_u, unif_i] of the forward."""
+    name, batch_word = "align_uniform_loss", "pairs"
+
+    def __init__(self, t, gamma):
+        self.t, self.gamma = t, gamma
+
+    def check(self, name, batch):
+        if batch.dim() != 2 or batch.shape[1] != 2:
+            raise _lib.TagrecError(f"{name}: a batch of shape {tuple(batch.shape)} does not fit the alignment / uniformity loss "
+                                   "(expected [B, 2] = user, positive; nothing is sampled)")
+        if batch.shape[0] < 2:
+            raise _lib.TagrecError(f"{name}: a batch of one pair (B = 1) has no other pair to be uniform against")
+
+    def fwd(self, batch, Ub, Ib, Ureg, Ireg):
+        res, self.extra, self.state = rowops.directau_fwd(Ub, Ib, Ureg, Ireg, self.t, self.gamma)
+        return res
+
+    def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
+        rowops.directau_bwd(Ub, Ib, Ureg, Ireg, self.state, g[:2], dUb, dIb, dUreg, dIreg, *self._what("directau_bwd", what))

@@ -20,6 +20,7 @@ from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
 from .base import layer_seed as _layer_seed
 from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
 from .graph import Graph, creat_adj
+from .loss_stage import Triplet
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
@@ -333,108 +334,59 @@ class _Propagate(torch.autograd.Function):
 
 
 class _PropagateBprLoss(torch.autograd.Function):
-    """(table, mats) -> [mul_loss, l2reg_loss(propagated rows)] in one autograd node."""
+    """(table, mats) -> [mul_loss, l2reg_loss(propagated rows)] in one autograd node; stage: the loss stage (loss_stage.py).
+    The L2 term reads the propagated rows, so both loss parts share their operands and one gradient buffer."""
 
     @staticmethod
-    def forward(ctx, graph, dims, n_user, n_item, trip, loss_kind, drops, seed, fused_opt, deterministic, rank, table, *mats):
+    def forward(ctx, graph, dims, n_user, n_item, batch, stage, drops, seed, fused_opt, deterministic, table, *mats):
         x0 = table.detach()
-        ctx.fused = (table, fused_opt) if fused_opt is not None else None
         wps = _wps([m.detach() for m in mats])
-        ctx.rank = rank
-        # rank = (K, temperature): a [B, 2 + K] tuple batch, the multi-negative kernels (rowops.rank_*);
-        # an H.InBatchRoute: a [B, 2] pair batch with in-batch negatives (rowops.inbatch_*)
-        if rank is not None:
-            return _PropagateBprLoss._forward_rank(ctx, graph, dims, n_user, trip, loss_kind, drops, seed, deterministic, x0, wps)
-        B, n = trip.shape[0], x0.shape[0]
-        rows = rowops.batch_rows(trip, n_user) if (RESTRICT_FORWARD or deterministic) else None
+        n = x0.shape[0]
+        # compact: the loss reads `out` at the batch rows only, and the top layers run on them alone (a batch that touches
+        # most rows gains nothing); on_tables: the triplet kernels gather from the full tables themselves
+        compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
+                       and batch.numel() * 16 <= n)
+        on_tables = not compact and isinstance(stage, Triplet)
+        rows = stage.rows(batch, n_user) if (RESTRICT_FORWARD or deterministic or not on_tables) else None
         # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
-        ctx.plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
-        ctx.graph, ctx.dims, ctx.trip, ctx.nu, ctx.ni = graph, dims, trip, n_user, n_item
-        ctx.compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
-                           and 3 * B * 16 <= n)                       # a batch that touches most rows gains nothing
-        if ctx.compact:
+        plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
+        B = batch.shape[0]
+        if compact:
             out_b, ctx.state = restricted_forward(graph, x0, wps, dims, rows)
-            ctrip = rowops.compact_triplets(B, x0.device)
+        else:
+            out, ctx.state = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
+        if on_tables:
+            res = stage.fwd_on_tables(batch, out, out, n_user, n_item)
+            ctx.out = out
+        else:
+            if not compact:                  # the kernels take gathered rows only
+                out_b = out.index_select(0, rows)
             U, I = out_b[:B], out_b[B:]
-            res, ctx.coef = rowops.bpr_fwd(U, I, U, I, ctrip, loss_kind)
-            ctx.rows, ctx.out_b, ctx.ctrip, ctx.n = rows, out_b, ctrip, n
-            return res
-        out, saved = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
-        U, I = out[:n_user], out[n_user:n_user + n_item]
-        res, ctx.coef = rowops.bpr_fwd(U, I, U, I, trip, loss_kind)
-        ctx.saved, ctx.out = saved, out
+            res = stage.fwd(batch, U, I, U, I)
+            ctx.out = out_b
+        ctx.fused = (table, fused_opt) if fused_opt is not None else None
+        ctx.graph, ctx.dims, ctx.stage, ctx.rows, ctx.plan, ctx.B, ctx.n = graph, dims, stage, rows, plan, B, n
+        ctx.compact, ctx.on_tables = compact, on_tables
         return res
-
-    @staticmethod
-    def _forward_rank(ctx, graph, dims, n_user, tuples, loss_kind, drops, seed, deterministic, x0, wps):
-        """The loss stage on `rowops.rank_fwd` / `rowops.inbatch_fwd`: only the row list changes, T = (2 + K) B (in-batch:
-        K = 0).  The all-rows path gathers the T rows of `out` (the kernels take compact rows only); the L2 term reads the same
-        propagated rows."""
-        B, n = tuples.shape[0], x0.shape[0]
-        rows = ctx.rows = rowops.tuple_rows(tuples, n_user)
-        ctx.plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
-        ctx.graph, ctx.dims, ctx.B, ctx.n = graph, dims, B, n
-        ctx.compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
-                           and rows.numel() * 16 <= n)              # a batch that touches most rows gains nothing
-        if ctx.compact:
-            out_b, ctx.state = restricted_forward(graph, x0, wps, dims, rows)
-        else:
-            out, ctx.saved = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
-            out_b = out.index_select(0, rows)
-        U, I = out_b[:B], out_b[B:]
-        ctx.in_batch = None
-        if isinstance(ctx.rank, H.InBatchRoute):
-            res, ctx.in_batch = H.in_batch_stage_fwd(ctx.rank, tuples, U, I, U, I)
-        else:
-            res, ctx.coef = rowops.rank_fwd(U, I, U, I, loss_kind, ctx.rank[1])
-        ctx.out_b = out_b
-        return res
-
-    @staticmethod
-    def _backward_rank(ctx, g):
-        out_b, B = ctx.out_b, ctx.B
-        d_b = torch.empty_like(out_b)                   # both loss parts land in one buffer; every row is stored by the kernel
-        U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
-        if ctx.in_batch is not None:
-            H.in_batch_stage_bwd(ctx.in_batch, U, I, U, I, g, dU, dI, dU, dI)
-            ctx.in_batch = None
-        else:
-            rowops.rank_bwd(U, I, U, I, ctx.coef, g, dU, dI, dU, dI)
-        if ctx.compact:
-            d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
-            ctx.state = None
-        else:
-            d_out = rowops.fold_rows(torch.zeros(ctx.n, out_b.shape[1], dtype=torch.float32, device=out_b.device), ctx.rows, d_b,
-                                     ctx.plan)
-            d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
-            ctx.saved = None
-        ctx.out_b = None
-        return (None,) * 11 + (d0, *_mat_grads(dws))
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.rank is not None:
-            return _PropagateBprLoss._backward_rank(ctx, g)
-        if ctx.compact:
-            out_b, ctrip = ctx.out_b, ctx.ctrip
-            B = ctrip.shape[0]
-            d_b = torch.zeros_like(out_b)
-            U, I, dU, dI = out_b[:B], out_b[B:], d_b[:B], d_b[B:]
-            rowops.bpr_bwd(U, I, U, I, ctrip, ctx.coef, g, dU, dI, dU, dI)
-            d0, dws = restricted_backward(ctx.graph.transpose(), ctx.rows, d_b, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
-            ctx.state = ctx.out_b = None
-            return (None,) * 11 + (d0, *_mat_grads(dws))
-        out, trip, nu, ni = ctx.out, ctx.trip, ctx.nu, ctx.ni
-        d_out = torch.zeros_like(out)
-        U, I = out[:nu], out[nu:nu + ni]
-        dU, dI = d_out[:nu], d_out[nu:nu + ni]
-        if ctx.plan is not None:
-            rowops.bpr_bwd_ordered(out, out, trip, ctx.coef, g, d_out, d_out, ctx.plan)
+        stage, out, B = ctx.stage, ctx.out, ctx.B
+        graph_t = ctx.graph.transpose()
+        d = (torch.zeros_like if stage.grads_zeroed else torch.empty_like)(out)    # both loss parts land in one buffer
+        if ctx.on_tables:
+            stage.bwd_on_tables(out, out, g, d, d, ctx.plan)
         else:
-            rowops.bpr_bwd(U, I, U, I, trip, ctx.coef, g, dU, dI, dU, dI)
-        d0, dws = propagate_backward(ctx.graph.transpose(), d_out, ctx.saved, ctx.dims)
-        ctx.saved = ctx.out = None
-        return (None,) * 11 + (d0, *_mat_grads(dws))
+            U, I, dU, dI = out[:B], out[B:], d[:B], d[B:]
+            stage.bwd(U, I, U, I, g, dU, dI, dU, dI)
+        if ctx.compact:
+            d0, dws = restricted_backward(graph_t, ctx.rows, d, ctx.state, ctx.dims, ctx.n, ctx.fused, ctx.plan)
+        else:
+            if not ctx.on_tables:
+                d = rowops.fold_rows(torch.zeros(ctx.n, out.shape[1], dtype=torch.float32, device=out.device), ctx.rows, d, ctx.plan)
+            d0, dws = propagate_backward(graph_t, d, ctx.state, ctx.dims)
+        ctx.state = ctx.out = None
+        return (None,) * 10 + (d0, *_mat_grads(dws))
 
 
 class NGCF(FusedStepModel):
@@ -509,25 +461,19 @@ class NGCF(FusedStepModel):
         batch_data = batch_data.to(self.device, torch.int64).contiguous()
         nu, ni = self.num_list[0], self.num_list[1]
         if self.in_batch:
-            rank = H.in_batch_route("NGCF", batch_data, self.loss_temperature, self.item_logq)
+            route = H.in_batch_route("NGCF", batch_data, self.loss_temperature, self.item_logq)
         else:
-            rank = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+            route = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
+        stage = H.stage_for(route, H.loss_kind_id(self.loss_func))
         if self.agg_type == "bi_agg" and self._fused_ok():
             drops, seed = self._drops()
             fused = fused_optimizer(self) if (self.training and torch.is_grad_enabled()) else None
-            res = _PropagateBprLoss.apply(self.norm_adj, tuple(self.dim_layer_list), nu, ni, batch_data,
-                                          H.loss_kind_id(self.loss_func), drops, seed, fused, self.deterministic, rank,
-                                          self.table, *self._mats())
-            return res[0], self.reg * res[1]
-        if self.deterministic:
+            res = _PropagateBprLoss.apply(self.norm_adj, tuple(self.dim_layer_list), nu, ni, batch_data, stage, drops, seed, fused,
+                                          self.deterministic, self.table, *self._mats())
+        elif self.deterministic:
             raise _lib.TagrecError("NGCF: deterministic=True covers the fused step only (bi_agg, widths in {16, 32, 64, 128}, "
                                    "no row folds)")
-        all_users, all_items = self.forward()[:2]
-        if self.in_batch:
-            loss, reg_loss = H.in_batch_loss(all_users, all_items, all_users, all_items, batch_data, rank.temperature, rank.item_logq)
-            return loss, self.reg * reg_loss
-        if rank is not None:
-            loss, reg_loss = H.ranking_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func, rank[1])
-            return loss, self.reg * reg_loss
-        loss, reg_loss = H.triplet_loss(all_users, all_items, all_users, all_items, batch_data, self.loss_func)
-        return loss, self.reg * reg_loss
+        else:
+            all_users, all_items = self.forward()[:2]
+            res = H.stage_loss(stage, all_users, all_items, all_users, all_items, batch_data)
+        return res[0], self.reg * res[1]

@@ -424,6 +424,42 @@ int tagrec_inbatch_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
                            int64_t B, float temperature, const float* lse, const float* g,
                            float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
 
+/* ---- Catalogue softmax: a fused rectangular B x N softmax cross-entropy, the logits are never stored (csrc/catsoftmax.hip) ----
+ * Q: float rows (stride ldq), row b of the problem is Q[qrow[b]] (qrow int64 [B]; NULL: row b).  T [N, D] (stride ldt): the
+ * column table.  target: int64 [B] in [0, N).  The kernels do not know what the operands stand for (users against the item
+ * catalogue, nodes against a centroid table).  Qreg (read at qrow) / Treg (read at target), width Dreg, stride ldreg: the rows
+ * the L2 term reads (both NULL: no L2 term); they may alias Q / T.
+ *   z_bn   = Q[qrow_b] . T[n] / temperature       (exact-fp32 MFMA 16x16x4, ascending feature blocks; one rounding for 1 / t)
+ *   loss_b = logsumexp_n z_bn - z_{b, target_b}   (>= 0 in floating point: zt comes from the tile that feeds the row sum)
+ * The column tiles (64 rows of T) are cut into n_split contiguous ranges of ceil(tiles / n_split) tiles, one block per (64-row
+ * tile of Q, range); a range past the last tile is empty.  n_split = 0: tagrec_catsoftmax_splits(B, N, D), the library's
+ * default (a pure function, >= 1); any other value in 1 .. 65535 is forced.  workspace: tagrec_catsoftmax_workspace(B, N, D,
+ * n_split) bytes, 4-byte aligned; nothing is kept in it between the forward and the backward.
+ * fwd writes lse [B], zt [B] (the target logit), loss_out[0] = mean_b (lse_b - zt_b) and loss_out[1] = 0.5 sum_b (|Qreg row|^2
+ * + |Treg row|^2) / B (unweighted; 0 without an L2 term).  Every row keeps a running (maximum, sum) per lane, started at a
+ * finite sentinel; lanes, then ranges (ascending, an empty one is (sentinel, 0)) are merged by one rescale and add each.
+ * D must be a multiple of 4 in 8 .. 256, 1 <= B <= 65536, N >= 1: anything else is TAGREC_E_UNSUPPORTED.  A target outside
+ * [0, N) is the caller's error: no access leaves the operands (the L2 read is clamped), zt[b] is then left unwritten. */
+int tagrec_catsoftmax_splits(int64_t B, int64_t N, int D);
+int64_t tagrec_catsoftmax_workspace(int64_t B, int64_t N, int D, int n_split);
+int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N, int D,
+                              const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg, int Dreg,
+                              int64_t B, float temperature, int n_split, void* workspace, int64_t workspace_bytes,
+                              float* lse, float* zt, float* loss_out, void* stream);
+/* bwd STORES (no atomics, no read of the old contents; the summation order is a function of (B, N, D, n_split) only)
+ *   dT[n]      = sum_b C_bn Q[qrow_b]             every row of the dense [N, D] (stride lddt), ascending b
+ *   dQ[b]      = sum_n C_bn T[n]                  every row of the compact, contiguous [B, D]: ascending n within a range
+ *                                                 (partial rows in the workspace), then ascending ranges
+ *   C_bn       = g0 / (temperature B) * (exp(z_bn - lse[b]) - [n == target_b])
+ *   dQreg[b]   = g1 / B * Qreg[qrow_b], dTreg[b] = g1 / B * Treg[target_b]     compact, contiguous [B, Dreg] (both NULL: not written)
+ * g = device pointer to two floats (upstream gradients of the two loss parts) or NULL for (1, 1).  dT = dQ = NULL: the L2
+ * part only.  Repeated qrow ids and repeated targets are the caller's to fold. */
+int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N, int D,
+                              const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg, int Dreg,
+                              int64_t B, float temperature, int n_split, void* workspace, int64_t workspace_bytes,
+                              const float* lse, const float* g, float* dT, int64_t lddt, float* dQ, float* dQreg, float* dTreg,
+                              void* stream);
+
 /* ---- DirectAU on COMPACT rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
  * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub; repeated rows are kept.
  * Ureg / Ireg [B, Dreg] (stride ldreg): the rows the L2 term reads (both NULL: no L2 term).  x^ = x / max(|x|, 1e-12).

@@ -34,6 +34,10 @@ def refuse_multi_negative(config, what):
     if config.get("model") == "directau":
         raise TagrecError(f"{what}: the \"directau\" configuration is not covered (alignment / uniformity loss: tagrec_amd.DirectAU "
                           "and BPR_training_data only)")
+    over = config.get("softmax_over", "negatives")
+    if over != "negatives":
+        raise TagrecError(f"{what}: softmax_over={over!r} is not covered (the softmax over the catalogue: the LightGCN and NGCF "
+                          "steps and BPR_training_data only); it takes softmax_over=\"negatives\"")
     neg = config.get("negatives", "sampled")
     if neg != "sampled":
         raise TagrecError(f"{what}: negatives={neg!r} is not covered (in-batch negatives: the LightGCN and NGCF steps and "
@@ -86,6 +90,14 @@ _SIGNATURES = {
                                c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_inbatch_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tagrec_catsoftmax_splits": [c_int64, c_int64, c_int],
+    "tagrec_catsoftmax_workspace": [c_int64, c_int64, c_int, c_int],
+    "tagrec_catsoftmax_fwd_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_int, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_void_p],
+    "tagrec_catsoftmax_bwd_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_int, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
     "tagrec_directau_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]
                                + [c_void_p] * 6,
     "tagrec_directau_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]

@@ -30,6 +30,8 @@ _BASE = {
     # where a positive's negatives come from (LightGCN, NGCF and BPR_training_data)
     "negatives": "sampled",       # "in_batch": the other positives of the batch (rowops.inbatch_*); batches are [B, 2], nothing is sampled
     "in_batch_logq": False,       # in-batch: subtract log(train degree of the item / train edges) from every column's logit
+    # what the "softmax" loss normalises over (LightGCN, NGCF and BPR_training_data)
+    "softmax_over": "negatives",  # "catalogue": every item (rowops.catsoftmax_*); batches are [B, 2], nothing is sampled
     # BPR_training_data: produce [E, 2] = (user, positive) epoch arrays without launching the sampler (the in-batch branch)
     # for objectives that take no negatives (DirectAU); the other producers do not read it
     "pair_batches": False,
@@ -38,6 +40,7 @@ NEG_SAMPLING_MODES = ("uniform", "popularity")
 MAX_NEG_CANDIDATES = 16
 MUL_LOSS_FUNCS = ("softplus", "logsigmoid", "softmax")
 NEGATIVES_MODES = ("sampled", "in_batch")
+SOFTMAX_OVER = ("negatives", "catalogue")
 MAX_NEGATIVES = 63                # the kernel keeps the K + 1 scores of a tuple one per lane of a 64-lane wavefront
 
 # utility/config.py:1-12, 41-52
@@ -77,6 +80,7 @@ def get_config(model="lightgcn", **overrides):
     check_neg_sampling(cfg)
     check_ranking(cfg)
     check_negatives(cfg)
+    check_softmax_over(cfg)
     if model == "simgcl":
         check_contrastive(cfg)
     if model == "directau":
@@ -128,6 +132,25 @@ def check_negatives(cfg):
     elif logq:
         raise TagrecError("in_batch_logq=True corrects in-batch negatives: it needs negatives=\"in_batch\"")
     return neg == "in_batch", logq
+
+
+def check_softmax_over(cfg):
+    """The softmax_over key of a config -> whether the softmax runs over the whole catalogue; an unknown value, and "catalogue"
+    with anything but mul_loss_func="softmax", n_negatives=1 and negatives="sampled" (it samples nothing and is not mixed with
+    in-batch negatives), is refused."""
+    from ._lib import TagrecError
+    over = cfg.get("softmax_over", "negatives")
+    if over not in SOFTMAX_OVER:
+        raise TagrecError(f"unknown softmax_over {over!r} (have {SOFTMAX_OVER})")
+    if over == "catalogue":
+        k, loss, neg = cfg.get("n_negatives", 1), cfg.get("mul_loss_func", "softplus"), cfg.get("negatives", "sampled")
+        if loss != "softmax":
+            raise TagrecError(f"softmax_over=\"catalogue\" is a softmax over every item: it needs mul_loss_func=\"softmax\", got {loss!r}")
+        if k != 1:
+            raise TagrecError(f"softmax_over=\"catalogue\" samples nothing: it needs n_negatives=1, got {k!r}")
+        if neg != "sampled":
+            raise TagrecError(f"softmax_over=\"catalogue\" is not mixed with negatives={neg!r}: it needs negatives=\"sampled\"")
+    return over == "catalogue"
 
 
 def check_contrastive(cfg):

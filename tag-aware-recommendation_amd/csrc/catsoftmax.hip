@@ -1,0 +1,548 @@
+// Catalogue softmax: a fused rectangular B x N softmax cross-entropy whose logits are never stored (tagrec_catsoftmax_fwd_f32 /
+// tagrec_catsoftmax_bwd_f32) -- the rectangular sibling of csrc/inbatch.hip, with csrc/eval.hip's walk over the whole table.
+//
+// Operands: Q (rows read at qrow[b]), T [N, D] the column table, target [B].  z_bn = Q[qrow_b] . T[n] / temperature.
+// The block shape is inbatch.hip's: four wavefronts OWN a tile of 64 rows of one operand and WALK the other operand in tiles
+// of 64 rows, both in LDS (row stride Dp + 4 floats); a wavefront holds 16 owned rows, its 16 x 64 score tile comes from the
+// exact-fp32 MFMA 16x16x4 (A = walked rows, B = owned rows), so lane (r = lane % 16, q = lane / 16) ends with the scores of
+// owned row r against the walked rows 16 t + 4 q + v.  What differs:
+//   * the long axis is N and IT is what the grid splits: the column tiles are cut into n_split contiguous ranges and one block
+//     serves one (64-row tile of Q, range) pair.  The forward leaves a (maximum, sum) pair per row and range, merged in
+//     ascending range order by cat_combine_kernel; the backward of Q leaves a partial row per range, summed in ascending
+//     range order by cat_sum_kernel.  An empty range (more ranges than tiles) leaves (sentinel, 0) / a zero row.
+//   * the walk is pipelined through registers: the global loads of the NEXT walked tile are issued before the MFMAs of the
+//     current one (NF float4 per thread, NF = Dp / 16), and land in LDS after the barrier that ends the current tile.
+//   * the backward of T is owned by a column tile that walks the B rows of Q (ascending b) and STORES its 64 rows of the dense
+//     dT: no atomics anywhere, nothing reads the old contents, every order is a function of (B, N, D, n_split) only.
+// The target logit zt[b] comes from the same MFMA tile that feeds the row sum (stored by the lane that meets column
+// target_b), so lse_b >= zt_b holds in floating point: the maximum is exact, the term of the maximum is exactly 1.
+#include "common.h"
+
+namespace tagrec {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kThreads = 256;
+constexpr int kTile = 64;                 // rows of the owned tile = rows of a walked tile = 16 per wavefront
+constexpr float kLowest = -3.0e38f;       // start of the running maximum: finite, below every score
+constexpr int kCombineRows = 256;         // rows per block of cat_combine_kernel: `partials` holds two floats per block
+constexpr int kMaxSplit = 65535;          // gridDim.y
+
+// rows of an operand as a tile walk sees them: row i is X[idx ? idx[i] : i], rows >= hi and columns >= D read as zero
+struct Rows {
+  const float* X;
+  int64_t ld;
+  const int64_t* idx;
+  int vec;                                // 16-byte aligned with ld % 4 == 0: float4 loads
+};
+
+struct CatArgs {
+  Rows q, t;
+  int64_t B, N;
+  int D, Dk;                              // Dk = D rounded up to 16 (score loop); the LDS row width Dp = 16 NF >= Dk
+  const int64_t* target;
+  float inv_tau, inv_b;
+  int64_t tiles_per_range;                // column tiles of one range; range y covers tiles y tpr .. (y + 1) tpr - 1
+  float* pm;                              // forward: [n_split, B] maxima and sums, zt [B]
+  float* ps;
+  float* zt;
+  const float* lse;                       // backward
+  const float* g;
+  float* dQpart;                          // [n_split, B, D] partial rows (dQ itself when n_split == 1)
+  float* dT;
+  int64_t lddt;
+};
+
+// rows row0 .. row0 + 63 -> NF float4 per thread (element idx = tid + 256 i of the [64, Dp / 4] tile)
+template <int NF>
+__device__ __forceinline__ void load_tile(f32x4 (&pre)[NF], const Rows& s, int D, int64_t row0, int64_t hi) {
+  constexpr int c4n = 4 * NF;
+#pragma unroll
+  for (int i = 0; i < NF; ++i) {
+    const int idx = threadIdx.x + kThreads * i;
+    const int row = idx / c4n, c = (idx - row * c4n) << 2;
+    const int64_t gr = row0 + row;
+    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (gr < hi && c < D) {
+      const float* p = s.X + (s.idx ? s.idx[gr] : gr) * s.ld + c;
+      if (s.vec) {
+        v = *reinterpret_cast<const f32x4*>(p);
+      } else {
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+      }
+    }
+    pre[i] = v;
+  }
+}
+
+template <int NF>
+__device__ __forceinline__ void store_tile(float* sh, const f32x4 (&pre)[NF]) {
+  constexpr int c4n = 4 * NF, S = 16 * NF + 4;
+#pragma unroll
+  for (int i = 0; i < NF; ++i) {
+    const int idx = threadIdx.x + kThreads * i;
+    const int row = idx / c4n, c = (idx - row * c4n) << 2;
+    *reinterpret_cast<f32x4*>(sh + row * S + c) = pre[i];
+  }
+}
+
+// MODE 0: forward (owner = 64 rows of Q, walks one column range).  MODE 1: backward of Q, the same roles.
+// MODE 2: backward of T (owner = 64 rows of T, walks all B rows of Q).
+template <int MODE, int NF>
+__device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) {
+  constexpr int Dp = 16 * NF, S = Dp + 4;
+  int64_t* sh_tgt = reinterpret_cast<int64_t*>(smem);  // MODE 2: targets and row log-sum-exps of the walked rows
+  float* sh_lse = reinterpret_cast<float*>(sh_tgt + kTile);
+  float* sh_own = sh_lse + kTile;
+  float* sh_walk = sh_own + kTile * S;
+
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const Rows& own = MODE == 2 ? a.t : a.q;
+  const Rows& walk = MODE == 2 ? a.q : a.t;
+  const int64_t own_n = MODE == 2 ? a.N : a.B;
+  const int64_t own0 = static_cast<int64_t>(blockIdx.x) * kTile;
+  int64_t w_begin = 0, w_end = a.B;
+  if (MODE != 2) {
+    const int64_t t0 = static_cast<int64_t>(blockIdx.y) * a.tiles_per_range;
+    w_begin = t0 * kTile;
+    w_end = (t0 + a.tiles_per_range) * kTile;
+    if (w_end > a.N) w_end = a.N;
+    if (w_begin > w_end) w_begin = w_end;              // an empty range
+  }
+
+  f32x4 pre[NF];
+  load_tile<NF>(pre, own, a.D, own0, own_n);
+  store_tile<NF>(sh_own, pre);
+
+  const int64_t o = own0 + 16 * wave + r;              // the owned row whose scores this lane ends up with
+  const bool o_ok = o < own_n;
+  const int64_t o_tgt = (MODE != 2 && o_ok) ? a.target[o] : -1;
+  const float o_lse = (MODE == 1 && o_ok) ? a.lse[o] : 0.f;
+  const float scale = MODE == 0 ? 0.f : ((a.g ? a.g[0] : 1.0f) * a.inv_tau) * a.inv_b;
+
+  float run_m = kLowest, run_s = 0.f;                  // forward: this lane's columns only
+  f32x4 acc[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (w_begin < w_end) load_tile<NF>(pre, walk, a.D, w_begin, w_end);
+  for (int64_t w0 = w_begin; w0 < w_end; w0 += kTile) {
+    __syncthreads();                                   // the previous walked tile has been consumed
+    store_tile<NF>(sh_walk, pre);
+    if (MODE == 2 && tid < kTile) {
+      const int64_t w = w0 + tid;
+      const bool ok = w < w_end;
+      sh_tgt[tid] = ok ? a.target[w] : -1;
+      sh_lse[tid] = ok ? a.lse[w] : 0.f;
+    }
+    __syncthreads();
+    if (w0 + kTile < w_end) load_tile<NF>(pre, walk, a.D, w0 + kTile, w_end);   // in flight under this tile's MFMAs
+
+    f32x4 sc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* po = sh_own + (16 * wave + r) * S + 4 * q;
+    const float* pw = sh_walk + r * S + 4 * q;
+    for (int kk = 0; kk < a.Dk; kk += 16) {
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(po + kk);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(pw + t * 16 * S + kk);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bv[c], sc[t], 0, 0, 0);
+      }
+    }
+    // sc[t][v] = owned row o . walked row w0 + 16 t + 4 q + v
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int wl = 16 * t + 4 * q + v;
+        const int64_t w = w0 + wl;
+        const bool live = o_ok && w < w_end;
+        const float z = sc[t][v] * a.inv_tau;          // one rounding, the same in every pass
+        if (MODE == 0) {
+          if (live) {
+            if (z > run_m) {
+              run_s = run_s * expf(run_m - z) + 1.0f;
+              run_m = z;
+            } else {
+              run_s += expf(z - run_m);
+            }
+            if (w == o_tgt) a.zt[o] = z;               // one lane of one block of the whole grid
+          }
+        } else {
+          const float l = MODE == 1 ? o_lse : sh_lse[wl];
+          const bool hit = MODE == 1 ? (w == o_tgt) : (sh_tgt[wl] == o);
+          sc[t][v] = live ? scale * (expf(z - l) - (hit ? 1.0f : 0.0f)) : 0.0f;
+        }
+      }
+    }
+    if (MODE != 0) {
+      // acc[f] += C [16 owned, 64 walked] . walked tile [64, 16 f .. 16 f + 15]; MFMA step (t, v) takes k = 16 t + 4 q + v
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const float* pb = sh_walk + (16 * t + 4 * q + v) * S + r;
+#pragma unroll
+          for (int f = 0; f < NF; ++f) acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(sc[t][v], pb[16 * f], acc[f], 0, 0, 0);
+        }
+      }
+    }
+  }
+
+  if (MODE == 0) {
+    // merge the four lanes of a row (q = 0 .. 3) in a fixed order; an empty lane holds (kLowest, 0)
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float m2 = __shfl_xor(run_m, off), s2 = __shfl_xor(run_s, off);
+      const float mn = fmaxf(run_m, m2);
+      run_s = run_s * expf(run_m - mn) + s2 * expf(m2 - mn);
+      run_m = mn;
+    }
+    if (o_ok && q == 0) {
+      const int64_t at = static_cast<int64_t>(blockIdx.y) * a.B + o;
+      a.pm[at] = run_m;
+      a.ps[at] = run_s;
+    }
+  } else {
+    // acc[f][v] = d owned row 16 wave + 4 q + v, column 16 f + r
+    float* dst = MODE == 1 ? a.dQpart + static_cast<int64_t>(blockIdx.y) * a.B * a.D : a.dT;
+    const int64_t ldd = MODE == 1 ? a.D : a.lddt;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      const int c = 16 * f + r;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int64_t row = own0 + 16 * wave + 4 * q + v;
+        if (row < own_n && c < a.D) dst[row * ldd + c] = acc[f][v];
+      }
+    }
+  }
+}
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) void cat_fwd_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<0, NF>(a, cat_smem);
+}
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) void cat_dq_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<1, NF>(a, cat_smem);
+}
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) void cat_dt_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<2, NF>(a, cat_smem);
+}
+
+struct RegArgs {
+  const float* Qreg;
+  const float* Treg;
+  const int64_t* qrow;
+  const int64_t* target;
+  int64_t ldreg, N;
+  int Dreg;
+};
+
+// row b of the two L2 operands; a target outside [0, N) is the caller's error and is clamped so that no read leaves Treg
+__device__ __forceinline__ const float* reg_row(const RegArgs& x, int side, int64_t b) {
+  if (side == 0) return x.Qreg + (x.qrow ? x.qrow[b] : b) * x.ldreg;
+  int64_t t = x.target[b];
+  t = t < 0 ? 0 : (t >= x.N ? x.N - 1 : t);
+  return x.Treg + t * x.ldreg;
+}
+
+// lse[b] = merge of the row's (maximum, sum) pairs in ascending range order; partials[2 blk] = sum of (lse - zt) over the
+// block's 256 rows (fixed tree), partials[2 blk + 1] = 0.5 sum |row|^2 of their L2 rows (one row per wavefront at a time)
+__global__ __launch_bounds__(kThreads) void cat_combine_kernel(const float* pm, const float* ps, int n_split, int64_t B,
+                                                               const float* zt, RegArgs x, float* lse_out, float* partials) {
+  __shared__ float sh[kThreads];
+  __shared__ float sh_reg[4];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kCombineRows, b = b0 + tid;
+  float loss = 0.f;
+  if (b < B) {
+    float m = kLowest, s = 0.f;
+    for (int y = 0; y < n_split; ++y) {
+      const float m2 = pm[static_cast<int64_t>(y) * B + b], s2 = ps[static_cast<int64_t>(y) * B + b];
+      const float mn = fmaxf(m, m2);
+      s = s * expf(m - mn) + s2 * expf(m2 - mn);
+      m = mn;
+    }
+    const float l = m + logf(s);                       // range 0 is never empty: m is a score, s >= 1
+    lse_out[b] = l;
+    loss = l - zt[b];
+  }
+  sh[tid] = loss;
+  float reg = 0.f;
+  if (x.Qreg) {
+    for (int side = 0; side < 2; ++side) {
+      for (int i = 0; i < kCombineRows / 4; ++i) {
+        const int64_t row = b0 + (kCombineRows / 4) * wave + i;
+        if (row >= B) break;
+        const float* p = reg_row(x, side, row);
+        float s = 0.f;
+        for (int c = lane; c < x.Dreg; c += 64) s = fmaf(p[c], p[c], s);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+        reg += s;
+      }
+    }
+  }
+  if (lane == 0) sh_reg[wave] = reg;
+  __syncthreads();
+  for (int off = kThreads / 2; off >= 1; off >>= 1) {
+    if (tid < off) sh[tid] += sh[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    partials[2 * blockIdx.x] = sh[0];
+    partials[2 * blockIdx.x + 1] = 0.5f * ((sh_reg[0] + sh_reg[1]) + (sh_reg[2] + sh_reg[3]));
+  }
+}
+
+// loss_out[k] = inv_b * sum over blocks of partials[2 i + k]: strided per-thread sums, then a fixed tree
+__global__ __launch_bounds__(kThreads) void cat_reduce_kernel(const float* partials, int64_t n, float inv_b, float* loss_out) {
+  __shared__ float sh[2][kThreads];
+  float s0 = 0.f, s1 = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += kThreads) {
+    s0 += partials[2 * i];
+    s1 += partials[2 * i + 1];
+  }
+  sh[0][threadIdx.x] = s0;
+  sh[1][threadIdx.x] = s1;
+  __syncthreads();
+  for (int off = kThreads / 2; off >= 1; off >>= 1) {
+    if (static_cast<int>(threadIdx.x) < off) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + off];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    loss_out[0] = sh[0][0] * inv_b;
+    loss_out[1] = sh[1][0] * inv_b;
+  }
+}
+
+// dQ[b] = sum over ranges of part[y][b], ascending y
+__global__ __launch_bounds__(kThreads) void cat_sum_kernel(const float* part, int n_split, int64_t BD, float* dQ) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= BD) return;
+  float s = part[i];
+  for (int y = 1; y < n_split; ++y) s += part[static_cast<int64_t>(y) * BD + i];
+  dQ[i] = s;
+}
+
+// the compact L2 gradients: dQreg[b] = rscale Qreg[qrow_b], dTreg[b] = rscale Treg[target_b], rscale = g1 / B
+__global__ __launch_bounds__(kThreads) void cat_reg_bwd_kernel(RegArgs x, int64_t B, const float* g, float inv_b, float* dQreg,
+                                                               float* dTreg) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= B * x.Dreg) return;
+  const int64_t b = i / x.Dreg;
+  const int c = static_cast<int>(i - b * x.Dreg);
+  const float rscale = (g ? g[1] : 1.0f) * inv_b;
+  dQreg[i] = rscale * reg_row(x, 0, b)[c];
+  dTreg[i] = rscale * reg_row(x, 1, b)[c];
+}
+
+size_t lds_bytes(int Dp) {
+  return kTile * sizeof(int64_t) + kTile * sizeof(float) + 2 * static_cast<size_t>(kTile) * (Dp + 4) * sizeof(float);
+}
+
+// the accumulator tiles the kernels are built for: the smallest NF with 16 NF >= D
+int pick_nf(int D) {
+  const int nfs[] = {1, 2, 4, 8, 12, 16};
+  for (int nf : nfs)
+    if (16 * nf >= D) return nf;
+  return 0;
+}
+
+bool shape_ok(int64_t B, int64_t N, int D) { return D >= 8 && D <= 256 && (D & 3) == 0 && B >= 1 && B <= 65536 && N >= 1; }
+
+int check_shape(const char* what, int64_t B, int64_t N, int D, int64_t ldq, int64_t ldt) {
+  if (D < 8 || D > 256 || (D & 3) != 0)
+    return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": D must be a multiple of 4 in 8 .. 256, got " + std::to_string(D));
+  if (B < 1 || B > 65536)
+    return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": B must be in 1 .. 65536, got " + std::to_string(B));
+  if (N < 1) return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": N must be >= 1, got " + std::to_string(N));
+  if (ldq < D || ldt < D) return fail(TAGREC_E_INVALID, std::string(what) + ": row stride below D");
+  return TAGREC_OK;
+}
+
+int64_t col_tiles(int64_t N) { return (N + kTile - 1) / kTile; }
+
+// row tiles x ranges fill the 256 CUs about four times over, and a range keeps at least four column tiles (the owned tile
+// is staged once per block)
+int default_splits(int64_t B, int64_t N) {
+  const int64_t row_tiles = (B + kTile - 1) / kTile;
+  int64_t want = (1024 + row_tiles - 1) / row_tiles;
+  const int64_t most = col_tiles(N) / 4;
+  if (want > most) want = most;
+  if (want > kMaxSplit) want = kMaxSplit;
+  return want < 1 ? 1 : static_cast<int>(want);
+}
+
+int resolve_splits(const char* what, int64_t B, int64_t N, int n_split, int* out) {
+  if (n_split < 0 || n_split > kMaxSplit)
+    return fail(TAGREC_E_INVALID, std::string(what) + ": n_split must be in 0 .. 65535 (0: the default), got " + std::to_string(n_split));
+  *out = n_split == 0 ? default_splits(B, N) : n_split;
+  return TAGREC_OK;
+}
+
+int64_t combine_blocks(int64_t B) { return (B + kCombineRows - 1) / kCombineRows; }
+
+// floats: the forward keeps pm | ps [n_split, B] each and two partials per combine block, the backward [n_split, B, D]
+int64_t workspace_floats(int64_t B, int D, int n_split) {
+  const int64_t fwd = 2 * static_cast<int64_t>(n_split) * B + 2 * combine_blocks(B);
+  const int64_t bwd = static_cast<int64_t>(n_split) * B * D;
+  return fwd > bwd ? fwd : bwd;
+}
+
+// Dynamic LDS past the default 64 KB (D > 112) needs the function attribute: it is set once per kernel instantiation and
+// device (the largest size asked for so far), so a later launch -- one inside a stream capture included -- makes no host call.
+template <void (*KERN)(CatArgs)>
+int launch(dim3 grid, size_t lds, const CatArgs& a, hipStream_t s) {
+  constexpr int kMaxDevices = 64;
+  static int granted[kMaxDevices] = {};
+  if (lds > 64 * 1024) {
+    int dev = 0;
+    TAGREC_HIP(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices || granted[dev] < static_cast<int>(lds)) {
+      TAGREC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+      if (dev >= 0 && dev < kMaxDevices) granted[dev] = static_cast<int>(lds);
+    }
+  }
+  KERN<<<grid, kThreads, lds, s>>>(a);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+#define TAGREC_CAT_DISPATCH(KERN, nf, grid, lds, a, s)                \
+  switch (nf) {                                                       \
+    case 1: rc = launch<KERN<1>>(grid, lds, a, s); break;             \
+    case 2: rc = launch<KERN<2>>(grid, lds, a, s); break;             \
+    case 4: rc = launch<KERN<4>>(grid, lds, a, s); break;             \
+    case 8: rc = launch<KERN<8>>(grid, lds, a, s); break;             \
+    case 12: rc = launch<KERN<12>>(grid, lds, a, s); break;           \
+    default: rc = launch<KERN<16>>(grid, lds, a, s); break;           \
+  }
+
+void fill_args(CatArgs& a, const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N, int D,
+               const int64_t* target, int64_t B, float temperature, int n_split) {
+  a.q.X = Q; a.q.ld = ldq; a.q.idx = qrow; a.q.vec = aligned16(Q) && (ldq & 3) == 0;
+  a.t.X = T; a.t.ld = ldt; a.t.idx = nullptr; a.t.vec = aligned16(T) && (ldt & 3) == 0;
+  a.B = B; a.N = N; a.D = D; a.Dk = (D + 15) & ~15;
+  a.target = target;
+  a.inv_tau = 1.0f / temperature; a.inv_b = 1.0f / static_cast<float>(B);
+  a.tiles_per_range = (col_tiles(N) + n_split - 1) / n_split;
+}
+
+}  // namespace
+}  // namespace tagrec
+
+using namespace tagrec;
+
+extern "C" int tagrec_catsoftmax_splits(int64_t B, int64_t N, int D) {
+  if (!shape_ok(B, N, D)) {
+    fail(TAGREC_E_UNSUPPORTED, "catsoftmax_splits: D a multiple of 4 in 8 .. 256, B in 1 .. 65536 and N >= 1 expected");
+    return TAGREC_E_UNSUPPORTED;
+  }
+  return default_splits(B, N);
+}
+
+extern "C" int64_t tagrec_catsoftmax_workspace(int64_t B, int64_t N, int D, int n_split) {
+  if (!shape_ok(B, N, D) || n_split < 0 || n_split > kMaxSplit) {
+    fail(TAGREC_E_UNSUPPORTED, "catsoftmax_workspace: D a multiple of 4 in 8 .. 256, B in 1 .. 65536, N >= 1 and n_split in "
+                               "0 .. 65535 expected");
+    return TAGREC_E_UNSUPPORTED;
+  }
+  return 4 * workspace_floats(B, D, n_split == 0 ? default_splits(B, N) : n_split);
+}
+
+extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                         int64_t workspace_bytes, float* lse, float* zt, float* loss_out, void* stream) {
+  if (int rc = check_shape("catsoftmax_fwd", B, N, D, ldq, ldt)) return rc;
+  TAGREC_REQUIRE(Q && T && target && workspace && lse && zt && loss_out, "catsoftmax_fwd: null pointer");
+  TAGREC_REQUIRE((Qreg == nullptr) == (Treg == nullptr), "catsoftmax_fwd: Qreg/Treg must both be given or both null");
+  TAGREC_REQUIRE(!Qreg || (Dreg >= 1 && ldreg >= Dreg), "catsoftmax_fwd: bad reg shape");
+  TAGREC_REQUIRE(temperature > 0.f && temperature <= 3.4028234e38f, "catsoftmax_fwd: the temperature must be finite and > 0");
+  int ns = 0;
+  if (int rc = resolve_splits("catsoftmax_fwd", B, N, n_split, &ns)) return rc;
+  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_fwd: the workspace is too small");
+  CatArgs a = {};
+  fill_args(a, Q, ldq, qrow, T, ldt, N, D, target, B, temperature, ns);
+  float* ws = static_cast<float*>(workspace);
+  a.pm = ws;
+  a.ps = ws + static_cast<int64_t>(ns) * B;
+  a.zt = zt;
+  float* partials = ws + 2 * static_cast<int64_t>(ns) * B;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nf = pick_nf(D);
+  const dim3 grid(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
+  const size_t lds = lds_bytes(16 * nf);
+  int rc = TAGREC_OK;
+  TAGREC_CAT_DISPATCH(cat_fwd_kernel, nf, grid, lds, a, s)
+  if (rc) return rc;
+  RegArgs x = {Qreg, Treg, qrow, target, ldreg, N, Dreg};
+  const int64_t blocks = combine_blocks(B);
+  cat_combine_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, s>>>(a.pm, a.ps, ns, B, zt, x, lse, partials);
+  TAGREC_LAUNCH_CHECK();
+  cat_reduce_kernel<<<1, kThreads, 0, s>>>(partials, blocks, a.inv_b, loss_out);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                         int64_t workspace_bytes, const float* lse, const float* g, float* dT, int64_t lddt,
+                                         float* dQ, float* dQreg, float* dTreg, void* stream) {
+  if (int rc = check_shape("catsoftmax_bwd", B, N, D, ldq, ldt)) return rc;
+  TAGREC_REQUIRE(Q && T && target && workspace && lse, "catsoftmax_bwd: null pointer");
+  TAGREC_REQUIRE((dT == nullptr) == (dQ == nullptr), "catsoftmax_bwd: dT/dQ must both be given or both null (the L2 part only)");
+  TAGREC_REQUIRE(dT || dQreg, "catsoftmax_bwd: nothing to write");
+  TAGREC_REQUIRE(!dT || lddt >= D, "catsoftmax_bwd: row stride of dT below D");
+  TAGREC_REQUIRE((dQreg == nullptr) == (dTreg == nullptr), "catsoftmax_bwd: dQreg/dTreg must both be given or both null");
+  TAGREC_REQUIRE(!dQreg || (Qreg && Treg && Dreg >= 1 && ldreg >= Dreg), "catsoftmax_bwd: bad reg arguments");
+  TAGREC_REQUIRE(temperature > 0.f && temperature <= 3.4028234e38f, "catsoftmax_bwd: the temperature must be finite and > 0");
+  int ns = 0;
+  if (int rc = resolve_splits("catsoftmax_bwd", B, N, n_split, &ns)) return rc;
+  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_bwd: the workspace is too small");
+  CatArgs a = {};
+  fill_args(a, Q, ldq, qrow, T, ldt, N, D, target, B, temperature, ns);
+  a.lse = lse; a.g = g; a.dT = dT; a.lddt = lddt;
+  a.dQpart = ns == 1 ? dQ : static_cast<float*>(workspace);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nf = pick_nf(D);
+  const size_t lds = lds_bytes(16 * nf);
+  int rc = TAGREC_OK;
+  if (dT) {
+    const dim3 grid_t(static_cast<unsigned>(col_tiles(N)));
+    TAGREC_CAT_DISPATCH(cat_dt_kernel, nf, grid_t, lds, a, s)
+    if (rc) return rc;
+    const dim3 grid_q(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
+    TAGREC_CAT_DISPATCH(cat_dq_kernel, nf, grid_q, lds, a, s)
+    if (rc) return rc;
+  }
+  if (dT && ns > 1) {
+    const int64_t BD = B * D;
+    cat_sum_kernel<<<static_cast<unsigned>((BD + kThreads - 1) / kThreads), kThreads, 0, s>>>(a.dQpart, ns, BD, dQ);
+    TAGREC_LAUNCH_CHECK();
+  }
+  if (dQreg) {
+    RegArgs x = {Qreg, Treg, qrow, target, ldreg, N, Dreg};
+    const int64_t n = B * Dreg;
+    cat_reg_bwd_kernel<<<static_cast<unsigned>((n + kThreads - 1) / kThreads), kThreads, 0, s>>>(x, B, g, a.inv_b, dQreg, dTreg);
+    TAGREC_LAUNCH_CHECK();
+  }
+  return TAGREC_OK;
+}

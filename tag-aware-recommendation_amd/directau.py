@@ -38,6 +38,9 @@ class DirectAU(LightGCN):
         if self.in_batch:
             raise _lib.TagrecError(f"{name}: the alignment / uniformity loss takes no negatives: it needs negatives=\"sampled\" "
                                    "(the default, unused), got \"in_batch\"")
+        if self.over_catalogue:
+            raise _lib.TagrecError(f"{name}: the alignment / uniformity loss is its own objective: it needs softmax_over=\"negatives\" "
+                                   "(the default, unused), got \"catalogue\"")
         self.au_gamma, self.au_t = check_alignment(config)
 
     def _route(self, batch_data):

@@ -158,6 +158,8 @@ def stage_loss(stage, U, I, Ureg, Ireg, batch, plans=None):
         if Ureg is not None and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr():
             Ureg, Ireg = U, I          # reg on the same rows: one gradient buffer
         return _TripletLoss.apply(U, I, Ureg, Ireg, batch, stage.loss_kind)
+    if stage.dense:                    # every row of I is an operand: nothing to gather
+        return _CatalogueLoss.apply(U, I, Ureg, Ireg, batch, stage, plans)
     return _GatheredRowsLoss.apply(U, I, Ureg, Ireg, batch, stage, plans)
 
 
@@ -235,6 +237,76 @@ def in_batch_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, item_logq=None, plan
     return out[0], out[1]
 
 
+class CatalogueRoute(NamedTuple):
+    """What a fused step is handed in place of `rank_route`'s (K, temperature) when the model has softmax_over="catalogue"."""
+    temperature: float
+
+
+def catalogue_route(model, batch, temperature):
+    """A model with softmax_over="catalogue" takes [B, 2] = (user, positive) batches; any other width is refused.
+    -> the `CatalogueRoute` its step takes."""
+    if batch.dim() != 2 or batch.shape[1] != 2:
+        raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit softmax_over=\"catalogue\" "
+                               "(expected [B, 2] = user, positive; every item of the catalogue is a column of the softmax)")
+    return CatalogueRoute(float(temperature))
+
+
+class _CatalogueLoss(torch.autograd.Function):
+    """The catalogue stage (loss_stage.Catalogue) on tables + a pair batch: the kernels read the user rows at the batch's ids
+    and walk the whole item table, the item gradient is stored dense and the compact user / L2 gradients are folded onto
+    their tables.  Returns [mul_loss, l2reg_loss (unweighted)]."""
+
+    @staticmethod
+    def forward(ctx, U, I, Ureg, Ireg, pairs, stage, plans):
+        name = stage.name
+        for t, nm in ((U, "U"), (I, "I"), (Ureg, "Ureg"), (Ireg, "Ireg")):
+            if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2):
+                raise _lib.TagrecError(f"{name}: {nm} must be a 2-d float32 GPU tensor")
+        pairs = _lib.require_gpu_tensor(pairs.contiguous(), torch.int64, f"{name} {stage.batch_word}")
+        stage.check(name, pairs)
+        urow, target = stage.ids(pairs)
+        has_reg = Ureg is not None
+        same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
+        res, lse, _ = rowops.catsoftmax_fwd(U, I, target, stage.temperature, urow, Ureg, Ireg)
+        ctx.save_for_backward(U, I, Ureg if has_reg else U.new_empty(0), Ireg if has_reg else U.new_empty(0), urow, target, lse)
+        ctx.tau, ctx.has_reg, ctx.same, ctx.plans = stage.temperature, has_reg, same, plans
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        U, I, Ureg, Ireg, urow, target, lse = ctx.saved_tensors
+        pu, pi = ctx.plans if ctx.plans is not None else (None, None)
+        B = urow.shape[0]
+        dI = torch.empty(I.shape, dtype=torch.float32, device=I.device)
+        dUr = dIr = None
+        if ctx.has_reg:
+            dUr, dIr = torch.empty(2, B, Ureg.shape[1], dtype=torch.float32, device=U.device)
+        else:
+            Ureg = Ireg = None
+        dQ = rowops.catsoftmax_bwd(U, I, target, ctx.tau, lse, g, dI, None, urow, Ureg, Ireg, dUr, dIr)
+        dU = rowops.fold_rows(torch.zeros(U.shape, dtype=torch.float32, device=U.device), urow, dQ, pu)
+        if not ctx.has_reg:
+            return dU, dI, None, None, None, None, None
+        if ctx.same:                           # reg on the same rows: the L2 rows join the two gradients
+            rowops.fold_rows(dU, urow, dUr, pu)
+            rowops.fold_rows(dI, target, dIr, pi)
+            return dU, dI, None, None, None, None, None
+        dUreg = rowops.fold_rows(torch.zeros(Ureg.shape, dtype=torch.float32, device=U.device), urow, dUr, pu)
+        dIreg = rowops.fold_rows(torch.zeros(Ireg.shape, dtype=torch.float32, device=U.device), target, dIr, pi)
+        return dU, dI, dUreg, dIreg, None, None, None
+
+
+def catalogue_softmax_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, plans=None):
+    """(mul_loss, l2reg_loss) of a [B, 2] batch (user, positive) under the full softmax: EVERY row of I is a column,
+    mul_loss = mean_b [logsumexp_n(u_b . i_n / temperature) - u_b . i_{p_b} / temperature]; nothing is sampled, masked or
+    corrected.  l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg (None: 0).  The B x n_item logits are never
+    stored; the gradient of I is dense.  The ids must lie inside the tables (not checked: that would take a host read).
+    plans (`in_batch_plans`): the compact user and L2 gradients are folded onto the tables in a fixed order (the same bits
+    every run) instead of by `index_add_`."""
+    out = stage_loss(S.Catalogue(float(temperature)), U, I, Ureg, Ireg, pairs, plans)
+    return out[0], out[1]
+
+
 class AuRoute(NamedTuple):
     """What a fused step is handed in place of `rank_route`'s value by a DirectAU model: the alignment / uniformity loss."""
     t: float                               # the Gaussian potential exp(-t |x - y|^2) of the uniformity term
@@ -256,6 +328,8 @@ def stage_for(route, loss_kind):
         return S.InBatch(*route)
     if isinstance(route, AuRoute):
         return S.Au(*route)
+    if isinstance(route, CatalogueRoute):
+        return S.Catalogue(*route)
     return S.Rank(loss_kind, route[1])
 
 

@@ -17,9 +17,8 @@ import torch
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking, check_softmax_over
 from .graph import EdgeDropView, Graph, creat_adj
-from .loss_stage import Triplet
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
@@ -264,9 +263,13 @@ class _PropagateBprLoss(torch.autograd.Function):
             ctx.ws = ws
         # compact: the loss reads `out` at the batch rows only, and the top layers run on them alone (a batch that touches
         # most rows gains nothing); on_tables: the triplet kernels gather from the full tables themselves
+        # a dense stage (every item row is a loss row) is never compact and nothing of its forward pass is row-masked
+        restrict = restrict and not stage.dense
         compact = bool(restrict and drops is None and n_layer >= 1 and graph.shape[0] == graph.shape[1] and D in VEC_WIDTHS
                        and batch.numel() * 16 <= n)
-        on_tables = not compact and isinstance(stage, Triplet)
+        on_tables = not compact and stage.on_tables
+        if stage.dense and not on_tables:
+            raise _lib.TagrecError(f"{stage.name}: a dense stage has the on-tables form only")
         rows = stage.rows(batch, n_user) if (restrict or deterministic or not on_tables) else None
         # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
         plan = row_plan(rows, n, D, ctx.ws) if deterministic else None
@@ -349,6 +352,8 @@ class LightGCN(FusedStepModel):
         self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
         # negatives="in_batch": [B, 2] batches, the other positives of the batch are the negatives (rowops.inbatch_*)
         self.in_batch, self.in_batch_logq = check_negatives(config)
+        # softmax_over="catalogue": [B, 2] batches, every item is a column of the user's softmax (rowops.catsoftmax_*)
+        self.over_catalogue = check_softmax_over(config)
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
         self.node_drop = config["node_drop"]
@@ -412,6 +417,8 @@ class LightGCN(FusedStepModel):
         """The loss stage of this model's step for `batch_data` (a subclass with another objective overrides it)."""
         if self.in_batch:
             return H.in_batch_route(type(self).__name__, batch_data, self.loss_temperature, self.item_logq)
+        if self.over_catalogue:
+            return H.catalogue_route(type(self).__name__, batch_data, self.loss_temperature)
         return H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
 
     def loss(self, batch_data):

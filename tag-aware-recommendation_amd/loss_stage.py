@@ -15,15 +15,22 @@ needs (coef / lse / AuState) on itself:
     stage.reg_apart                        True: a step whose L2 rows are not its loss rows launches the backward once per part
     stage.extra                            None, or a device tensor the forward leaves to be appended to `res` (no gradient)
 
+    stage.on_tables                        True: the stage has the second form below, and an all-rows step takes it
+    stage.dense                            True: the stage reads EVERY item row, so it has the second form only -- its step is
+                                           never compact and nothing of its forward pass may be row-masked
+
 `Triplet` has a second form, `fwd_on_tables` / `bwd_on_tables`, for the all-rows step: its kernels take the real triplets and
-gather from the full tables themselves, so that step has no gathered rows at all.
+gather from the full tables themselves, so that step has no gathered rows at all.  `Catalogue` has that form alone.
 """
+import torch
+
+
 from . import _lib, rowops
 
 
 class _Stage:
     name = batch_word = None                 # the table loss of this stage in help.py and what it calls its batch
-    grads_zeroed = reg_apart = False
+    grads_zeroed = reg_apart = on_tables = dense = False
     extra = None
     _ids = None
 
@@ -42,7 +49,7 @@ class _Stage:
 
 class Triplet(_Stage):
     """[B, 3] = (user, positive, negative): `rowops.bpr_fwd` / `bpr_bwd` on `compact_triplets` of the gathered rows."""
-    grads_zeroed = True
+    grads_zeroed = on_tables = True
 
     def __init__(self, loss_kind):
         self.loss_kind = loss_kind
@@ -140,3 +147,57 @@ class Au(_Stage):
 
     def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
         rowops.directau_bwd(Ub, Ib, Ureg, Ireg, self.state, g[:2], dUb, dIb, dUreg, dIreg, *self._what("directau_bwd", what))
+
+
+class Catalogue(_Stage):
+    """[B, 2] = (user, positive) under the full softmax: every item of the catalogue is a column of the user's softmax
+    (`rowops.catsoftmax_fwd` / `catsoftmax_bwd`; the B x n_item logits are never stored).  Nothing is sampled or masked."""
+    name, batch_word = "catalogue_softmax_loss", "pairs"
+    grads_zeroed = on_tables = dense = True      # the dense store covers the item block only: the rest of d_out arrives zeroed
+
+    def __init__(self, temperature):
+        self.temperature = temperature
+
+    def check(self, name, batch):
+        if batch.dim() != 2 or batch.shape[1] != 2:
+            raise _lib.TagrecError(f"{name}: pairs {tuple(batch.shape)} must be [B, 2] = (user, positive)")
+
+    def fwd_on_tables(self, batch, out, ego, n_user, n_item):
+        """The stage on the full [user | item] tables `out` (and `ego`: the L2 part's, or None): the users' rows are read
+        at batch[:, 0] by the kernel, the item block is the column table."""
+        self._cut = lambda t: (None, None) if t is None else (t[:n_user], t[n_user:n_user + n_item])
+        self.n_user = n_user
+        self.urow, self.target = self.ids(batch)
+        res, self.lse, _ = rowops.catsoftmax_fwd(*self._cut(out), self.target, self.temperature, self.urow, *self._cut(ego))
+        return res
+
+    def bwd_on_tables(self, out, ego, g, d_out, d_ego, plan=None, what=None):
+        """d_out (zeroed outside its item block by the caller): the item block is STORED by the kernel, then the compact user
+        gradients are folded onto the user rows; ego / d_ego (None: no L2 part): the compact L2 rows are folded onto d_ego
+        last -- d_ego may be d_out.  d_out None: the L2 part only, added to what d_ego holds.
+        plan (the `row_list_plan` of `rows`, users then items): both folds run in a fixed order, no float atomics."""
+        B, D = self.urow.shape[0], out.shape[1]
+        kw = {} if what is None else {"what": f"catsoftmax_bwd({what})"}
+        d_e = dQr = dTr = None
+        if ego is not None and d_ego is not None:
+            d_e = torch.empty(2 * B, ego.shape[1], dtype=torch.float32, device=out.device)
+            dQr, dTr = d_e[:B], d_e[B:]
+        Ue, Ie = self._cut(ego if d_e is not None else None)
+        if d_out is not None:
+            # through a plan the user gradients travel as the first B of the plan's 2 B slots; the item slots add zero
+            d_q = torch.zeros(2 * B, D, dtype=torch.float32, device=out.device) if plan is not None else \
+                torch.empty(B, D, dtype=torch.float32, device=out.device)
+            rowops.catsoftmax_bwd(*self._cut(out), self.target, self.temperature, self.lse, g, self._cut(d_out)[1], d_q[:B],
+                                  self.urow, Ue, Ie, dQr, dTr, **kw)
+            if plan is not None:
+                rowops.scatter_rows_ordered(d_out, plan, d_q, True)
+            else:
+                d_out[:self.n_user].index_add_(0, self.urow, d_q)
+        elif d_e is not None:
+            rowops.catsoftmax_bwd(*self._cut(out), self.target, self.temperature, self.lse, g, None, None, self.urow, Ue, Ie,
+                                  dQr, dTr, **kw)
+        if d_e is not None:
+            rowops.fold_rows(d_ego, plan.rows if plan is not None else self.rows_of(), d_e, plan)
+
+    def rows_of(self):
+        return torch.cat([self.urow, self.n_user + self.target])

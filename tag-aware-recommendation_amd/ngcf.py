@@ -18,9 +18,8 @@ import torch.nn as nn
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking, check_softmax_over
 from .graph import Graph, creat_adj
-from .loss_stage import Triplet
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
 
@@ -344,17 +343,19 @@ class _PropagateBprLoss(torch.autograd.Function):
         n = x0.shape[0]
         # compact: the loss reads `out` at the batch rows only, and the top layers run on them alone (a batch that touches
         # most rows gains nothing); on_tables: the triplet kernels gather from the full tables themselves
-        compact = bool(RESTRICT_FORWARD and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
+        # a dense stage (every item row is a loss row) is never compact and nothing of its forward pass is row-masked
+        restrict = RESTRICT_FORWARD and not stage.dense
+        compact = bool(restrict and drops is None and len(wps) >= 1 and graph.shape[0] == graph.shape[1]
                        and batch.numel() * 16 <= n)
-        on_tables = not compact and isinstance(stage, Triplet)
-        rows = stage.rows(batch, n_user) if (RESTRICT_FORWARD or deterministic or not on_tables) else None
+        on_tables = not compact and stage.on_tables
+        rows = stage.rows(batch, n_user) if (restrict or deterministic or not on_tables) else None
         # deterministic: one sorted plan of the batch rows per step; every fold of compact gradients goes through it
         plan = rowops.row_list_plan(rows, n, None, sum(dims)) if deterministic else None
         B = batch.shape[0]
         if compact:
             out_b, ctx.state = restricted_forward(graph, x0, wps, dims, rows)
         else:
-            out, ctx.state = propagate_forward(graph, x0, wps, dims, rows if RESTRICT_FORWARD else None, drops, seed, deterministic)
+            out, ctx.state = propagate_forward(graph, x0, wps, dims, rows if restrict else None, drops, seed, deterministic)
         if on_tables:
             res = stage.fwd_on_tables(batch, out, out, n_user, n_item)
             ctx.out = out
@@ -422,6 +423,8 @@ class NGCF(FusedStepModel):
         self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
         # negatives="in_batch": [B, 2] batches, the other positives of the batch are the negatives (rowops.inbatch_*)
         self.in_batch, self.in_batch_logq = check_negatives(config)
+        # softmax_over="catalogue": [B, 2] batches, every item is a column of the user's softmax (rowops.catsoftmax_*)
+        self.over_catalogue = check_softmax_over(config)
         self.use_tag = config["use_tag"]
         self.drop_seed = config.get("seed", 2020)
         # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
@@ -462,6 +465,8 @@ class NGCF(FusedStepModel):
         nu, ni = self.num_list[0], self.num_list[1]
         if self.in_batch:
             route = H.in_batch_route("NGCF", batch_data, self.loss_temperature, self.item_logq)
+        elif self.over_catalogue:
+            route = H.catalogue_route("NGCF", batch_data, self.loss_temperature)
         else:
             route = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         stage = H.stage_for(route, H.loss_kind_id(self.loss_func))

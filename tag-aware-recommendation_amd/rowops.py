@@ -300,6 +300,123 @@ def inbatch_bwd(Ub, Ib, Ureg, Ireg, temperature, lse, g, dUb, dIb, dUreg, dIreg,
                                         ptr(dIreg), stream_ptr()), what)
 
 
+# ---- catalogue softmax: the fused rectangular B x N softmax cross-entropy (csrc/catsoftmax.hip) ----
+
+def catsoftmax_splits(B, N, D):
+    """The library's default number of column ranges for a [B, N] problem of width D (a pure function, >= 1)."""
+    n = load().tagrec_catsoftmax_splits(B, N, D)
+    if n < 1:
+        check(n, "catsoftmax_splits")
+    return n
+
+
+def catsoftmax_workspace(B, N, D, n_split=0):
+    """Bytes of the workspace of `catsoftmax_fwd` / `catsoftmax_bwd` (n_split = 0: the default split)."""
+    nbytes = load().tagrec_catsoftmax_workspace(B, N, D, n_split)
+    if nbytes <= 0:
+        check(-1, "catsoftmax_workspace")
+    return nbytes
+
+
+def _row_ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _catsoftmax_args(what, Q, T, target, qrow, Qreg, Treg, n_split, workspace):
+    """(B, N, D, ldreg, Dreg, workspace) of a catalogue-softmax call after the checks the two kernels share.  The VALUES of
+    target (in [0, N)) and qrow (rows of Q / Qreg) are not checked: that would take a host read."""
+    for nm, t in (("Q", Q), ("T", T), ("Qreg", Qreg), ("Treg", Treg)):
+        if t is None and nm in ("Qreg", "Treg"):
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise _lib.TagrecError(f"{what}: {nm} must be a 2-d float32 GPU tensor")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise _lib.TagrecError(f"{what}: {nm} must have unit inner stride, got {t.stride(1)}")
+    if Q.shape[1] != T.shape[1]:
+        raise _lib.TagrecError(f"{what}: Q {tuple(Q.shape)} and T {tuple(T.shape)} must be of one width")
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.int64 or target.dim() != 1 or not target.is_contiguous() \
+            or target.device != Q.device:
+        raise _lib.TagrecError(f"{what}: target must be a contiguous int64 tensor of shape [B] on {Q.device}")
+    B, N, D = target.shape[0], T.shape[0], Q.shape[1]
+    if B < 1:
+        raise _lib.TagrecError(f"{what}: an empty batch (B = 0) has no loss")
+    if N < 1:
+        raise _lib.TagrecError(f"{what}: an empty column table (N = 0) has no softmax")
+    if qrow is None:
+        if Q.shape[0] != B:
+            raise _lib.TagrecError(f"{what}: without qrow, Q {tuple(Q.shape)} must have one row per target ({B})")
+    elif qrow.dtype != torch.int64 or qrow.shape != (B,) or not qrow.is_contiguous() or qrow.device != Q.device:
+        raise _lib.TagrecError(f"{what}: qrow must be a contiguous int64 tensor of shape [{B}] on {Q.device}")
+    if (Qreg is None) != (Treg is None):
+        raise _lib.TagrecError(f"{what}: Qreg / Treg must both be given or both None")
+    ldreg = dreg = 0
+    if Qreg is not None:
+        if Qreg.shape[1] != Treg.shape[1] or Qreg.shape[0] != Q.shape[0] or Treg.shape[0] != N:
+            raise _lib.TagrecError(f"{what}: Qreg {tuple(Qreg.shape)} / Treg {tuple(Treg.shape)} must have the rows of Q "
+                                   f"({Q.shape[0]}) / T ({N}) and one width")
+        dreg = Qreg.shape[1]
+        lds = {_row_ld(t) for t in (Qreg, Treg) if t.shape[0] > 1}
+        if len(lds) > 1:
+            raise _lib.TagrecError(f"{what}: Qreg and Treg are indexed with one row stride, got {sorted(lds)}")
+        ldreg = lds.pop() if lds else dreg
+    if isinstance(n_split, bool) or not isinstance(n_split, int) or not 0 <= n_split <= 65535:
+        raise _lib.TagrecError(f"{what}: n_split must be an integer in 0 .. 65535 (0: the library's default), got {n_split!r}")
+    need = catsoftmax_workspace(B, N, D, n_split)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=Q.device)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != Q.device or not workspace.is_contiguous():
+        raise _lib.TagrecError(f"{what}: the workspace must be a contiguous uint8 tensor of >= {need} bytes on {Q.device}")
+    return B, N, D, ldreg, dreg, workspace
+
+
+def catsoftmax_fwd(Q, T, target, temperature, qrow=None, Qreg=None, Treg=None, n_split=0, workspace=None):
+    """Softmax cross-entropy of B rows against EVERY row of T: z_bn = Q[qrow[b]] . T[n] / temperature (qrow None: row b),
+    loss_b = logsumexp_n z_bn - z_{b, target[b]}; Qreg / Treg (read at qrow / target; None: no L2 term) the L2 rows.
+    -> (res = [mean_b loss_b, l2reg_loss (unweighted)], lse [B] for `catsoftmax_bwd`, zt [B] the target logits).
+    The B x N logits are never stored.  n_split: column ranges the walk is cut into (0: `catsoftmax_splits`).  target must lie
+    in [0, N) and qrow in the rows of Q: neither is checked (the kernels keep their reads inside the operands regardless)."""
+    B, N, D, ldreg, dreg, workspace = _catsoftmax_args("catsoftmax_fwd", Q, T, target, qrow, Qreg, Treg, n_split, workspace)
+    small = torch.empty(2 * B + 2, dtype=torch.float32, device=Q.device)         # lse | zt | res
+    lse, zt, res = small[:B], small[B:2 * B], small[2 * B:]
+    check(load().tagrec_catsoftmax_fwd_f32(ptr(Q), _row_ld(Q), ptr(qrow), ptr(T), _row_ld(T), N, D, ptr(target), ptr(Qreg), ptr(Treg),
+                                           ldreg, dreg, B, float(temperature), n_split, ptr(workspace), workspace.numel(), ptr(lse),
+                                           ptr(zt), ptr(res), stream_ptr()), "catsoftmax_fwd")
+    return res, lse, zt
+
+
+def catsoftmax_bwd(Q, T, target, temperature, lse, g, dT, dQ=None, qrow=None, Qreg=None, Treg=None, dQreg=None, dTreg=None,
+                   n_split=0, workspace=None, what="catsoftmax_bwd"):
+    """STORES the gradients of `catsoftmax_fwd`'s two loss parts (g = their upstream gradients, two floats; None: both 1):
+    every row of the dense dT [N, D] (may be a strided view) and of the compact dQ [B, D] (None: allocated) -- no atomics, the
+    old contents are not read, the same bits for one (B, N, D, n_split).  dQreg / dTreg [B, Dreg] (both None: not written):
+    the compact L2 gradients of the rows Qreg[qrow] / Treg[target]; dT = dQ = None: they alone.  Folding repeated qrow ids / targets is the caller's.
+    -> dQ."""
+    B, N, D, ldreg, dreg, workspace = _catsoftmax_args(what, Q, T, target, qrow, Qreg, Treg, n_split, workspace)
+    g = None if g is None else g.contiguous()
+    if lse.shape != (B,) or not lse.is_contiguous() or lse.dtype != torch.float32:
+        raise _lib.TagrecError(f"{what}: lse {tuple(lse.shape)} must be a contiguous float32 [{B}] tensor")
+    if dT is None:                           # the L2 part only
+        if dQ is not None or dQreg is None:
+            raise _lib.TagrecError(f"{what}: without dT, dQ must be None too and dQreg / dTreg are what is written")
+    elif dQ is None:
+        dQ = torch.empty(B, D, dtype=torch.float32, device=Q.device)
+    if dT is None:
+        pass
+    elif dT.dim() != 2 or dT.shape != (N, D) or dT.dtype != torch.float32 or not dT.is_cuda or dT.stride(1) != 1:
+        raise _lib.TagrecError(f"{what}: dT {tuple(dT.shape)} must be a float32 GPU tensor [{N}, {D}] with unit inner stride")
+    if dQ is not None and (dQ.shape != (B, D) or dQ.dtype != torch.float32 or not dQ.is_contiguous()):
+        raise _lib.TagrecError(f"{what}: dQ {tuple(dQ.shape)} must be a contiguous float32 [{B}, {D}] tensor")
+    if (dQreg is None) != (dTreg is None) or (dQreg is not None and Qreg is None):
+        raise _lib.TagrecError(f"{what}: dQreg / dTreg must both be given (with Qreg / Treg) or both None")
+    for nm, t in (("dQreg", dQreg), ("dTreg", dTreg)):
+        if t is not None and (t.shape != (B, dreg) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must be a contiguous float32 [{B}, {dreg}] tensor")
+    check(load().tagrec_catsoftmax_bwd_f32(ptr(Q), _row_ld(Q), ptr(qrow), ptr(T), _row_ld(T), N, D, ptr(target), ptr(Qreg), ptr(Treg),
+                                           ldreg, dreg, B, float(temperature), n_split, ptr(workspace), workspace.numel(), ptr(lse),
+                                           ptr(g), ptr(dT), 0 if dT is None else _row_ld(dT), ptr(dQ), ptr(dQreg), ptr(dTreg), stream_ptr()), what)
+    return dQ
+
+
 # ---- DirectAU on compact rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
 
 AU_PREP_ROWS = 4         # batch positions per block of the prep kernel: `partials` holds two floats per block of it ...

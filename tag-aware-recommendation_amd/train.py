@@ -7,6 +7,7 @@ fused Adam that replaces `torch.optim.Adam` (com.py:14,25,69).
     Early_stop                                                         training/early_stop.py:8-41
     Adam(params, lr)   zero_grad()/step()                              torch.optim.Adam defaults
 """
+import gc
 import os
 import time
 
@@ -210,8 +211,17 @@ class GraphedStep:
         self._opts = opts
         before = [op.step_count for op in opts]
         [op.zero_grad() for op in opts]
-        with torch.cuda.graph(self.graph):
-            self.static_parts = _step(loss_func, opt, self.static_batch)
+        # No destructor may free device memory inside the capture (`Graph.__del__` ends in hipFree, which invalidates it), and
+        # torch no longer collects before one: collect what is dead now and keep the cycle collector off until the capture ends.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.static_parts = _step(loss_func, opt, self.static_batch)
+        finally:
+            if gc_was_on:
+                gc.enable()
         for op, b in zip(opts, before):          # capturing executed nothing: the host-side counters follow the replays
             op.step_count = b
 

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import CFG as _GLOBAL_CFG, check_neg_sampling, check_negatives, check_ranking
+from .config import CFG as _GLOBAL_CFG, check_neg_sampling, check_negatives, check_ranking, check_softmax_over
 
 
 def alias_table(weights):
@@ -164,8 +164,8 @@ def _sampler_keys(cfg, pos):
 
 class BPR_training_data(Abstract_training_data):
     """config["n_negatives"] = K negatives per train edge (default one: [E, 3] triplets; else [E, 2 + K] tuples), re-drawn
-    and shuffled every epoch; config["negatives"] = "in_batch" or config["pair_batches"] = True: [E, 2] pairs, nothing is
-    drawn, the shuffle is the same.
+    and shuffled every epoch; config["negatives"] = "in_batch", config["softmax_over"] = "catalogue" or
+    config["pair_batches"] = True: [E, 2] pairs, nothing is drawn, the shuffle is the same.
     With config["neg_candidates"] > 1 the epoch's
     negatives are scored by `model` (given here or through `attach_model`): one eval-mode, no-grad `model.forward()` per
     epoch supplies the user and item tables `predict_rating` scores with."""
@@ -186,7 +186,8 @@ class BPR_training_data(Abstract_training_data):
         pair = cfg.get("pair_batches", False)
         if not isinstance(pair, bool):
             raise _lib.TagrecError(f"pair_batches must be True or False, got {pair!r}")
-        self._in_batch = check_negatives(cfg)[0] or pair
+        # softmax_over="catalogue" (every item is a column: nothing to draw) takes it too
+        self._in_batch = check_negatives(cfg)[0] or pair or check_softmax_over(cfg)
         self._model = model
         self._seed = int(cfg["seed"] if seed is None else seed)
         self._epoch = 0

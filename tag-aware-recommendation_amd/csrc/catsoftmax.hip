@@ -2,10 +2,8 @@
 // tagrec_catsoftmax_bwd_f32) -- the rectangular sibling of csrc/inbatch.hip, with csrc/eval.hip's walk over the whole table.
 //
 // Operands: Q (rows read at qrow[b]), T [N, D] the column table, target [B].  z_bn = Q[qrow_b] . T[n] / temperature.
-// The block shape is inbatch.hip's: four wavefronts OWN a tile of 64 rows of one operand and WALK the other operand in tiles
-// of 64 rows, both in LDS (row stride Dp + 4 floats); a wavefront holds 16 owned rows, its 16 x 64 score tile comes from the
-// exact-fp32 MFMA 16x16x4 (A = walked rows, B = owned rows), so lane (r = lane % 16, q = lane / 16) ends with the scores of
-// owned row r against the walked rows 16 t + 4 q + v.  What differs:
+// The tile scheme is the one of csrc/pairtile.h (owned tile x walked tile in LDS, score MFMA, running (maximum, sum), C fed
+// straight to the second MFMA).  What is this loss's own:
 //   * the long axis is N and IT is what the grid splits: the column tiles are cut into n_split contiguous ranges and one block
 //     serves one (64-row tile of Q, range) pair.  The forward leaves a (maximum, sum) pair per row and range, merged in
 //     ascending range order by cat_combine_kernel; the backward of Q leaves a partial row per range, summed in ascending
@@ -16,26 +14,13 @@
 //     dT: no atomics anywhere, nothing reads the old contents, every order is a function of (B, N, D, n_split) only.
 // The target logit zt[b] comes from the same MFMA tile that feeds the row sum (stored by the lane that meets column
 // target_b), so lse_b >= zt_b holds in floating point: the maximum is exact, the term of the maximum is exactly 1.
-#include "common.h"
+#include "pairtile.h"
 
 namespace tagrec {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kThreads = 256;
-constexpr int kTile = 64;                 // rows of the owned tile = rows of a walked tile = 16 per wavefront
-constexpr float kLowest = -3.0e38f;       // start of the running maximum: finite, below every score
 constexpr int kCombineRows = 256;         // rows per block of cat_combine_kernel: `partials` holds two floats per block
 constexpr int kMaxSplit = 65535;          // gridDim.y
-
-// rows of an operand as a tile walk sees them: row i is X[idx ? idx[i] : i], rows >= hi and columns >= D read as zero
-struct Rows {
-  const float* X;
-  int64_t ld;
-  const int64_t* idx;
-  int vec;                                // 16-byte aligned with ld % 4 == 0: float4 loads
-};
 
 struct CatArgs {
   Rows q, t;
@@ -54,50 +39,18 @@ struct CatArgs {
   int64_t lddt;
 };
 
-// rows row0 .. row0 + 63 -> NF float4 per thread (element idx = tid + 256 i of the [64, Dp / 4] tile)
-template <int NF>
-__device__ __forceinline__ void load_tile(f32x4 (&pre)[NF], const Rows& s, int D, int64_t row0, int64_t hi) {
-  constexpr int c4n = 4 * NF;
-#pragma unroll
-  for (int i = 0; i < NF; ++i) {
-    const int idx = threadIdx.x + kThreads * i;
-    const int row = idx / c4n, c = (idx - row * c4n) << 2;
-    const int64_t gr = row0 + row;
-    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (gr < hi && c < D) {
-      const float* p = s.X + (s.idx ? s.idx[gr] : gr) * s.ld + c;
-      if (s.vec) {
-        v = *reinterpret_cast<const f32x4*>(p);
-      } else {
-        v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
-      }
-    }
-    pre[i] = v;
-  }
-}
-
-template <int NF>
-__device__ __forceinline__ void store_tile(float* sh, const f32x4 (&pre)[NF]) {
-  constexpr int c4n = 4 * NF, S = 16 * NF + 4;
-#pragma unroll
-  for (int i = 0; i < NF; ++i) {
-    const int idx = threadIdx.x + kThreads * i;
-    const int row = idx / c4n, c = (idx - row * c4n) << 2;
-    *reinterpret_cast<f32x4*>(sh + row * S + c) = pre[i];
-  }
-}
-
 // MODE 0: forward (owner = 64 rows of Q, walks one column range).  MODE 1: backward of Q, the same roles.
 // MODE 2: backward of T (owner = 64 rows of T, walks all B rows of Q).
 template <int MODE, int NF>
 __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) {
-  constexpr int Dp = 16 * NF, S = Dp + 4;
+  constexpr int S = tile_stride(16 * NF);
   int64_t* sh_tgt = reinterpret_cast<int64_t*>(smem);  // MODE 2: targets and row log-sum-exps of the walked rows
   float* sh_lse = reinterpret_cast<float*>(sh_tgt + kTile);
   float* sh_own = sh_lse + kTile;
   float* sh_walk = sh_own + kTile * S;
 
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const PairLane ln = pair_lane();
+  const int tid = threadIdx.x, wave = ln.wave, r = ln.r, q = ln.q;
   const Rows& own = MODE == 2 ? a.t : a.q;
   const Rows& walk = MODE == 2 ? a.q : a.t;
   const int64_t own_n = MODE == 2 ? a.N : a.B;
@@ -122,9 +75,8 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
   const float scale = MODE == 0 ? 0.f : ((a.g ? a.g[0] : 1.0f) * a.inv_tau) * a.inv_b;
 
   float run_m = kLowest, run_s = 0.f;                  // forward: this lane's columns only
-  f32x4 acc[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+  AccTiles<NF> acc;
+  zero_acc(acc);
 
   if (w_begin < w_end) load_tile<NF>(pre, walk, a.D, w_begin, w_end);
   for (int64_t w0 = w_begin; w0 < w_end; w0 += kTile) {
@@ -140,19 +92,7 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
     if (w0 + kTile < w_end) load_tile<NF>(pre, walk, a.D, w0 + kTile, w_end);   // in flight under this tile's MFMAs
 
     f32x4 sc[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* po = sh_own + (16 * wave + r) * S + 4 * q;
-    const float* pw = sh_walk + r * S + 4 * q;
-    for (int kk = 0; kk < a.Dk; kk += 16) {
-      const f32x4 bv = *reinterpret_cast<const f32x4*>(po + kk);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const f32x4 av = *reinterpret_cast<const f32x4*>(pw + t * 16 * S + kk);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) sc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c], bv[c], sc[t], 0, 0, 0);
-      }
-    }
+    score_tile(sh_own, sh_walk, S, a.Dk, ln, sc);
     // sc[t][v] = owned row o . walked row w0 + 16 t + 4 q + v
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -164,12 +104,7 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
         const float z = sc[t][v] * a.inv_tau;          // one rounding, the same in every pass
         if (MODE == 0) {
           if (live) {
-            if (z > run_m) {
-              run_s = run_s * expf(run_m - z) + 1.0f;
-              run_m = z;
-            } else {
-              run_s += expf(z - run_m);
-            }
+            lse_push(run_m, run_s, z);
             if (w == o_tgt) a.zt[o] = z;               // one lane of one block of the whole grid
           }
         } else {
@@ -179,36 +114,17 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
         }
       }
     }
-    if (MODE != 0) {
-      // acc[f] += C [16 owned, 64 walked] . walked tile [64, 16 f .. 16 f + 15]; MFMA step (t, v) takes k = 16 t + 4 q + v
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const float* pb = sh_walk + (16 * t + 4 * q + v) * S + r;
-#pragma unroll
-          for (int f = 0; f < NF; ++f) acc[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(sc[t][v], pb[16 * f], acc[f], 0, 0, 0);
-        }
-      }
-    }
+    if (MODE != 0) grad_tile<NF>(sh_walk, S, ln, sc, acc);
   }
 
   if (MODE == 0) {
-    // merge the four lanes of a row (q = 0 .. 3) in a fixed order; an empty lane holds (kLowest, 0)
-#pragma unroll
-    for (int off = 16; off <= 32; off <<= 1) {
-      const float m2 = __shfl_xor(run_m, off), s2 = __shfl_xor(run_s, off);
-      const float mn = fmaxf(run_m, m2);
-      run_s = run_s * expf(run_m - mn) + s2 * expf(m2 - mn);
-      run_m = mn;
-    }
+    lse_merge_q(run_m, run_s);
     if (o_ok && q == 0) {
       const int64_t at = static_cast<int64_t>(blockIdx.y) * a.B + o;
       a.pm[at] = run_m;
       a.ps[at] = run_s;
     }
   } else {
-    // acc[f][v] = d owned row 16 wave + 4 q + v, column 16 f + r
     float* dst = MODE == 1 ? a.dQpart + static_cast<int64_t>(blockIdx.y) * a.B * a.D : a.dT;
     const int64_t ldd = MODE == 1 ? a.D : a.lddt;
 #pragma unroll
@@ -217,7 +133,7 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         const int64_t row = own0 + 16 * wave + 4 * q + v;
-        if (row < own_n && c < a.D) dst[row * ldd + c] = acc[f][v];
+        if (row < own_n && c < a.D) dst[row * ldd + c] = acc.f[f][v];
       }
     }
   }
@@ -264,38 +180,21 @@ __global__ __launch_bounds__(kThreads) void cat_combine_kernel(const float* pm, 
                                                                const float* zt, RegArgs x, float* lse_out, float* partials) {
   __shared__ float sh[kThreads];
   __shared__ float sh_reg[4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const PairLane ln = pair_lane();
+  const int tid = threadIdx.x;
   const int64_t b0 = static_cast<int64_t>(blockIdx.x) * kCombineRows, b = b0 + tid;
   float loss = 0.f;
   if (b < B) {
     float m = kLowest, s = 0.f;
-    for (int y = 0; y < n_split; ++y) {
-      const float m2 = pm[static_cast<int64_t>(y) * B + b], s2 = ps[static_cast<int64_t>(y) * B + b];
-      const float mn = fmaxf(m, m2);
-      s = s * expf(m - mn) + s2 * expf(m2 - mn);
-      m = mn;
-    }
+    for (int y = 0; y < n_split; ++y) lse_merge(m, s, pm[static_cast<int64_t>(y) * B + b], ps[static_cast<int64_t>(y) * B + b]);
     const float l = m + logf(s);                       // range 0 is never empty: m is a score, s >= 1
     lse_out[b] = l;
     loss = l - zt[b];
   }
   sh[tid] = loss;
   float reg = 0.f;
-  if (x.Qreg) {
-    for (int side = 0; side < 2; ++side) {
-      for (int i = 0; i < kCombineRows / 4; ++i) {
-        const int64_t row = b0 + (kCombineRows / 4) * wave + i;
-        if (row >= B) break;
-        const float* p = reg_row(x, side, row);
-        float s = 0.f;
-        for (int c = lane; c < x.Dreg; c += 64) s = fmaf(p[c], p[c], s);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        reg += s;
-      }
-    }
-  }
-  if (lane == 0) sh_reg[wave] = reg;
+  if (x.Qreg) reg = l2_rows([&](int side, int64_t row) { return reg_row(x, side, row); }, b0, kCombineRows / 4, B, x.Dreg, ln);
+  if (ln.lane == 0) sh_reg[ln.wave] = reg;
   __syncthreads();
   for (int off = kThreads / 2; off >= 1; off >>= 1) {
     if (tid < off) sh[tid] += sh[tid + off];
@@ -307,28 +206,8 @@ __global__ __launch_bounds__(kThreads) void cat_combine_kernel(const float* pm, 
   }
 }
 
-// loss_out[k] = inv_b * sum over blocks of partials[2 i + k]: strided per-thread sums, then a fixed tree
 __global__ __launch_bounds__(kThreads) void cat_reduce_kernel(const float* partials, int64_t n, float inv_b, float* loss_out) {
-  __shared__ float sh[2][kThreads];
-  float s0 = 0.f, s1 = 0.f;
-  for (int64_t i = threadIdx.x; i < n; i += kThreads) {
-    s0 += partials[2 * i];
-    s1 += partials[2 * i + 1];
-  }
-  sh[0][threadIdx.x] = s0;
-  sh[1][threadIdx.x] = s1;
-  __syncthreads();
-  for (int off = kThreads / 2; off >= 1; off >>= 1) {
-    if (static_cast<int>(threadIdx.x) < off) {
-      sh[0][threadIdx.x] += sh[0][threadIdx.x + off];
-      sh[1][threadIdx.x] += sh[1][threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    loss_out[0] = sh[0][0] * inv_b;
-    loss_out[1] = sh[1][0] * inv_b;
-  }
+  reduce_loss_pair(partials, n, inv_b, loss_out);
 }
 
 // dQ[b] = sum over ranges of part[y][b], ascending y
@@ -353,27 +232,15 @@ __global__ __launch_bounds__(kThreads) void cat_reg_bwd_kernel(RegArgs x, int64_
 }
 
 size_t lds_bytes(int Dp) {
-  return kTile * sizeof(int64_t) + kTile * sizeof(float) + 2 * static_cast<size_t>(kTile) * (Dp + 4) * sizeof(float);
-}
-
-// the accumulator tiles the kernels are built for: the smallest NF with 16 NF >= D
-int pick_nf(int D) {
-  const int nfs[] = {1, 2, 4, 8, 12, 16};
-  for (int nf : nfs)
-    if (16 * nf >= D) return nf;
-  return 0;
+  return kTile * sizeof(int64_t) + kTile * sizeof(float) + tiles_bytes(Dp);
 }
 
 bool shape_ok(int64_t B, int64_t N, int D) { return D >= 8 && D <= 256 && (D & 3) == 0 && B >= 1 && B <= 65536 && N >= 1; }
 
 int check_shape(const char* what, int64_t B, int64_t N, int D, int64_t ldq, int64_t ldt) {
-  if (D < 8 || D > 256 || (D & 3) != 0)
-    return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": D must be a multiple of 4 in 8 .. 256, got " + std::to_string(D));
-  if (B < 1 || B > 65536)
-    return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": B must be in 1 .. 65536, got " + std::to_string(B));
+  if (int rc = check_rows(what, B, 1, "", D)) return rc;
   if (N < 1) return fail(TAGREC_E_UNSUPPORTED, std::string(what) + ": N must be >= 1, got " + std::to_string(N));
-  if (ldq < D || ldt < D) return fail(TAGREC_E_INVALID, std::string(what) + ": row stride below D");
-  return TAGREC_OK;
+  return check_stride(what, ldq < ldt ? ldq : ldt, D);
 }
 
 int64_t col_tiles(int64_t N) { return (N + kTile - 1) / kTile; }
@@ -405,40 +272,11 @@ int64_t workspace_floats(int64_t B, int D, int n_split) {
   return fwd > bwd ? fwd : bwd;
 }
 
-// Dynamic LDS past the default 64 KB (D > 112) needs the function attribute: it is set once per kernel instantiation and
-// device (the largest size asked for so far), so a later launch -- one inside a stream capture included -- makes no host call.
-template <void (*KERN)(CatArgs)>
-int launch(dim3 grid, size_t lds, const CatArgs& a, hipStream_t s) {
-  constexpr int kMaxDevices = 64;
-  static int granted[kMaxDevices] = {};
-  if (lds > 64 * 1024) {
-    int dev = 0;
-    TAGREC_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices || granted[dev] < static_cast<int>(lds)) {
-      TAGREC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      if (dev >= 0 && dev < kMaxDevices) granted[dev] = static_cast<int>(lds);
-    }
-  }
-  KERN<<<grid, kThreads, lds, s>>>(a);
-  TAGREC_LAUNCH_CHECK();
-  return TAGREC_OK;
-}
-
-#define TAGREC_CAT_DISPATCH(KERN, nf, grid, lds, a, s)                \
-  switch (nf) {                                                       \
-    case 1: rc = launch<KERN<1>>(grid, lds, a, s); break;             \
-    case 2: rc = launch<KERN<2>>(grid, lds, a, s); break;             \
-    case 4: rc = launch<KERN<4>>(grid, lds, a, s); break;             \
-    case 8: rc = launch<KERN<8>>(grid, lds, a, s); break;             \
-    case 12: rc = launch<KERN<12>>(grid, lds, a, s); break;           \
-    default: rc = launch<KERN<16>>(grid, lds, a, s); break;           \
-  }
-
 void fill_args(CatArgs& a, const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N, int D,
                const int64_t* target, int64_t B, float temperature, int n_split) {
   a.q.X = Q; a.q.ld = ldq; a.q.idx = qrow; a.q.vec = aligned16(Q) && (ldq & 3) == 0;
   a.t.X = T; a.t.ld = ldt; a.t.idx = nullptr; a.t.vec = aligned16(T) && (ldt & 3) == 0;
-  a.B = B; a.N = N; a.D = D; a.Dk = (D + 15) & ~15;
+  a.B = B; a.N = N; a.D = D; a.Dk = round16(D);
   a.target = target;
   a.inv_tau = 1.0f / temperature; a.inv_b = 1.0f / static_cast<float>(B);
   a.tiles_per_range = (col_tiles(N) + n_split - 1) / n_split;
@@ -474,7 +312,7 @@ extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int6
   TAGREC_REQUIRE(Q && T && target && workspace && lse && zt && loss_out, "catsoftmax_fwd: null pointer");
   TAGREC_REQUIRE((Qreg == nullptr) == (Treg == nullptr), "catsoftmax_fwd: Qreg/Treg must both be given or both null");
   TAGREC_REQUIRE(!Qreg || (Dreg >= 1 && ldreg >= Dreg), "catsoftmax_fwd: bad reg shape");
-  TAGREC_REQUIRE(temperature > 0.f && temperature <= 3.4028234e38f, "catsoftmax_fwd: the temperature must be finite and > 0");
+  if (int rc = check_temperature("catsoftmax_fwd", temperature)) return rc;
   int ns = 0;
   if (int rc = resolve_splits("catsoftmax_fwd", B, N, n_split, &ns)) return rc;
   TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_fwd: the workspace is too small");
@@ -489,9 +327,7 @@ extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int6
   const int nf = pick_nf(D);
   const dim3 grid(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
   const size_t lds = lds_bytes(16 * nf);
-  int rc = TAGREC_OK;
-  TAGREC_CAT_DISPATCH(cat_fwd_kernel, nf, grid, lds, a, s)
-  if (rc) return rc;
+  if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_fwd_kernel<decltype(n)::value>>(grid, lds, a, s); })) return rc;
   RegArgs x = {Qreg, Treg, qrow, target, ldreg, N, Dreg};
   const int64_t blocks = combine_blocks(B);
   cat_combine_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, s>>>(a.pm, a.ps, ns, B, zt, x, lse, partials);
@@ -513,7 +349,7 @@ extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int6
   TAGREC_REQUIRE(!dT || lddt >= D, "catsoftmax_bwd: row stride of dT below D");
   TAGREC_REQUIRE((dQreg == nullptr) == (dTreg == nullptr), "catsoftmax_bwd: dQreg/dTreg must both be given or both null");
   TAGREC_REQUIRE(!dQreg || (Qreg && Treg && Dreg >= 1 && ldreg >= Dreg), "catsoftmax_bwd: bad reg arguments");
-  TAGREC_REQUIRE(temperature > 0.f && temperature <= 3.4028234e38f, "catsoftmax_bwd: the temperature must be finite and > 0");
+  if (int rc = check_temperature("catsoftmax_bwd", temperature)) return rc;
   int ns = 0;
   if (int rc = resolve_splits("catsoftmax_bwd", B, N, n_split, &ns)) return rc;
   TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_bwd: the workspace is too small");
@@ -524,14 +360,11 @@ extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nf = pick_nf(D);
   const size_t lds = lds_bytes(16 * nf);
-  int rc = TAGREC_OK;
   if (dT) {
     const dim3 grid_t(static_cast<unsigned>(col_tiles(N)));
-    TAGREC_CAT_DISPATCH(cat_dt_kernel, nf, grid_t, lds, a, s)
-    if (rc) return rc;
+    if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_dt_kernel<decltype(n)::value>>(grid_t, lds, a, s); })) return rc;
     const dim3 grid_q(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
-    TAGREC_CAT_DISPATCH(cat_dq_kernel, nf, grid_q, lds, a, s)
-    if (rc) return rc;
+    if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_dq_kernel<decltype(n)::value>>(grid_q, lds, a, s); })) return rc;
   }
   if (dT && ns > 1) {
     const int64_t BD = B * D;

@@ -3,13 +3,24 @@
 The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).  There
 is deliberately no fallback: if the shared object is missing, or a call fails,
 `TagrecError` is raised -- nothing here computes on the CPU.
+
+include/tagrec.h is the only statement of the signatures: `load()` parses its prototypes and sets every function's
+argtypes and restype from them, so a new entry point is declared in the header and wrapped where it is used, nothing
+else.  A pointer parameter's argtype is one of a handful of classes (`Ptr` and its per-dtype subclasses) whose
+`from_param` takes the tensor itself: a tensor whose dtype is not the header's pointee type, or one that is not on a
+GPU, is refused with `ctypes.ArgumentError` before anything is launched.  Contiguity is not checked (strided slot views
+with an `ld` argument are deliberate).  `ptr()` stays for raw callers and for the few deliberate reinterpretations.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_void_p
+import re
+from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtagrec_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tagrec.h")       # where csrc/common.h includes it from
 ABI_VERSION = 2
 
 LOSS_SOFTPLUS = 0
@@ -48,222 +59,100 @@ def refuse_multi_negative(config, what):
                           "LightGCN and NGCF steps and BPR_training_data only); it takes n_negatives=1 and softplus / logsigmoid")
 
 
-# name -> (argtypes); every function returns int except the two noted below
-_SIGNATURES = {
-    "tagrec_abi_version": [],
-    "tagrec_device_info": [POINTER(c_int), POINTER(c_int), c_char_p, c_int],
-    "tagrec_graph_create": [POINTER(c_void_p), c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_graph_create_like": [POINTER(c_void_p), c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_graph_workspace": [c_int64],
-    "tagrec_graph_create_ws": [POINTER(c_void_p), c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                               c_void_p],
-    "tagrec_graph_create_ws_deferred": [POINTER(c_void_p), c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                        c_void_p],
-    "tagrec_graph_create_like_ws": [POINTER(c_void_p), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64],
-    "tagrec_graph_destroy": [c_void_p],
-    "tagrec_graph_info": [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
-                          POINTER(c_int64)],
-    "tagrec_spmm_f32": [c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_norm_acc_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p],
-    "tagrec_spmm_normbwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_axpy_f32": [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_ss_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_normbwd_dot_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int,
-                                    c_void_p],
-    "tagrec_row_scale_acc_f32": [c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_row_dot_f32": [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_rownorm_bwd_dot_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_bpr_dots_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
-                            c_void_p, c_void_p],
-    "tagrec_rownorm_fwd_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_rownorm_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int, c_int64, c_int,
-                               c_void_p],
-    "tagrec_bpr_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
-                           c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_bpr_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
-                           c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_rank_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_int,
-                            c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_rank_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p,
-                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_inbatch_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                               c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_inbatch_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                               c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_catsoftmax_splits": [c_int64, c_int64, c_int],
-    "tagrec_catsoftmax_workspace": [c_int64, c_int64, c_int, c_int],
-    "tagrec_catsoftmax_fwd_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_int64, c_int, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                  c_void_p],
-    "tagrec_catsoftmax_bwd_f32": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_int64, c_int, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_directau_fwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]
-                               + [c_void_p] * 6,
-    "tagrec_directau_bwd_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_float, c_float]
-                               + [c_void_p] * 8,
-    "tagrec_ngcf_wgrad_workspace": [c_int, c_int],
-    "tagrec_ngcf_dense_fwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                  c_void_p, c_int64, c_void_p],
-    "tagrec_ngcf_dense_bwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_ngcf_dense_bwd_norm_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_ngcf_wgrad_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                              c_void_p, c_int64, c_void_p],
-    "tagrec_ngcf_dense_fwd_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_ngcf_dense_bwd_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_void_p],
-    "tagrec_ngcf_wgrad_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                   c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_tgcn_attn_workspace": [c_int, c_int],
-    "tagrec_tgcn_attn_fwd_f32": [c_void_p] * 7 + [c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    "tagrec_tgcn_attn_bwd_f32": [c_void_p] * 9 + [c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 7 + [c_int64, c_void_p],
-    "tagrec_attn_pull_da_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_attn_invert_fill": [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_tgcn_attn_bwd_ds_f32": [c_void_p] * 8 + [c_int64, c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p],
-    "tagrec_attn_pull_dq_f32": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
-    "tagrec_attn_seg_dq_f32": [c_void_p, c_void_p, c_int64, ctypes.c_int32, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "tagrec_nbr_gather_i32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    "tagrec_plan_flags_workspace": [c_void_p],
-    "tagrec_plan_segment_result": [c_void_p, c_int],
-    "tagrec_plan_scan_workspace": [c_void_p],
-    "tagrec_plan_mark_u8": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                            c_void_p, c_void_p],
-    "tagrec_plan_compact_i64": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
-    "tagrec_plan_lookup_i64": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p],
-    "tagrec_inv_filter_workspace": [c_int64],
-    "tagrec_inv_filter_i32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int64, c_void_p,
-                              c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
-    "tagrec_attn_keys_i32": [c_void_p, c_int64, ctypes.c_int32, c_void_p, c_void_p],
-    "tagrec_tgcn_fuse_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 12,
-    "tagrec_tgcn_fuse_fwd_drop_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 9
-                                     + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
-    "tagrec_tgcn_fuse_bwd_workspace": [c_int],
-    "tagrec_tgcn_fuse_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 18
-                                + [c_int64, c_void_p],
-    "tagrec_tgcn_fuse_wf_workspace": [c_int, c_int],
-    "tagrec_tgcn_fuse_wf_result": [c_int, c_int],
-    "tagrec_tgcn_fuse_wf_f32": [c_void_p] * 10 + [c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p],
-    "tagrec_route_softmax_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_route_rowsum_rsqrt_f32": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "tagrec_route_permute_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_route_spmm_f32": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
-                              c_void_p, c_int, c_void_p],
-    "tagrec_route_score_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
-    "tagrec_route_spmm_ex_f32": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
-                                 c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_route_score_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p],
-    "tagrec_slice_scale_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
-    "tagrec_slice_norm_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p],
-    "tagrec_slice_norm_bwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p],
-    "tagrec_row_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_row_softmax_bwd_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_spmm_norm_acc_drop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, ctypes.c_uint64, c_int,
-                                      c_void_p],
-    "tagrec_spmm_normbwd_drop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, ctypes.c_uint64, c_void_p,
-                                     c_int, c_void_p],
-    "tagrec_dropout_f32": [c_void_p, c_void_p, c_int64, c_float, ctypes.c_uint64, c_void_p],
-    "tagrec_dropout_rows_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, ctypes.c_uint64, c_void_p],
-    "tagrec_rownorm_bwd_flags_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int, c_int64, c_int, c_void_p,
-                                     c_void_p, c_void_p],
-    "tagrec_spmm_normbwd_sparse_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                       ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_axpy_sparse_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_void_p],
-    "tagrec_spmm_normbwd_dot_sparse_f32": [c_void_p] * 8 + [c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_graph_mark_rows_u8": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_graph_mark_cols_u8": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_spmm_norm_acc_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, ctypes.c_uint64,
-                                      c_int, c_void_p],
-    "tagrec_spmm_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_ss_rows_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_flags_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_spmm_listed_workspace": [c_int64, c_int],
-    "tagrec_spmm_listed_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p],
-    # edge dropout inside the products (adj.py:170-191): the product's own arguments + (ed_p, ed_seed, ed_transposed)
-    "tagrec_edge_drop_mask_u8": [c_void_p, c_float, ctypes.c_uint64, c_int, c_void_p, c_void_p],
-    "tagrec_spmm_edrop_f32": [c_void_p, c_void_p, c_void_p, c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
-    "tagrec_spmm_norm_acc_rows_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float,
-                                            ctypes.c_uint64, c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
-    "tagrec_spmm_normbwd_sparse_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                             ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
-                                             ctypes.c_uint64, c_int, c_int, c_void_p],
-    "tagrec_spmm_axpy_sparse_edrop_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
-                                          c_float, ctypes.c_uint64, c_int, c_int, c_void_p],
-    "tagrec_spmm_listed_edrop_f32": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_float,
-                                     ctypes.c_uint64, c_int, c_void_p],
-    # noise perturbation of the SimGCL views inside the layer kernels: (eps, seed, view, layer) key the direction by node id
-    "tagrec_spmm_norm_acc_noise_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float,
-                                       ctypes.c_uint64, c_int, c_int, c_int, c_void_p],
-    "tagrec_noise_rownorm_fwd_f32": [c_void_p, c_void_p, c_int64, c_float, ctypes.c_uint64, c_int, c_int, c_void_p, c_int64,
-                                     c_void_p, c_int, c_void_p],
-    "tagrec_noise_dir_f32": [c_void_p, c_void_p, c_int64, ctypes.c_uint64, c_int, c_int, c_int, c_void_p],
-    "tagrec_batch_hop_workspace": [c_int64, c_int64, c_int64],
-    "tagrec_batch_hop_grid_rows": [c_int],
-    "tagrec_batch_hop_list_result": [c_int64, c_int64, c_int64, c_int],
-    "tagrec_batch_hop_plan": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_batch_hop_normbwd_f32": [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_rowlist_workspace": [c_int64, c_int],
-    "tagrec_rowlist_plan_result": [c_int64, c_int, c_int],
-    "tagrec_rowlist_plan_i64": [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p],
-    "tagrec_row_scatter_ordered_f32": [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
-                                       c_int, c_void_p],
-    "tagrec_row_flags_f32": [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p],
-    "tagrec_dh_edge_softmax_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
-    "tagrec_dh_edge_softmax_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
-                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_dh_rel_epi_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_dh_rel_epi_bwd_f32": [c_void_p] * 7 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_dh_combine_fwd_f32": [c_void_p] * 5 + [c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_dh_combine_bwd_f32": [c_void_p] * 7 + [c_int64, c_int, c_int] + [c_void_p] * 6,
-    "tagrec_eval_topk_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p,
-                             c_void_p, c_void_p],
-    "tagrec_eval_topk_auc_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_sample_negative_i64": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p],
-    "tagrec_sample_negative_ex_i64": [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, ctypes.c_uint64, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_void_p],
-    "tagrec_transtag_fwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_void_p, c_void_p,
-                                c_void_p, c_void_p],
-    "tagrec_transtag_bwd_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float, c_void_p, c_void_p,
-                                c_void_p, c_void_p, c_void_p, c_void_p],
-    "tagrec_spmm_axpy_adam_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_float, c_float, c_float, c_float, c_int64, c_int, c_void_p],
-    "tagrec_tall_mm_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
-                           c_void_p, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_tall_mm_adam_f32": [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-                                c_float, c_float, c_float, c_float, c_int64, c_void_p],
-    "tagrec_tall_wgrad_workspace": [c_int, c_int],
-    "tagrec_tall_wgrad_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
-                              c_void_p, c_int64, c_void_p],
-    "tagrec_small_mm_f32": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p],
-    "tagrec_masked_colsum_workspace": [c_int],
-    "tagrec_masked_colsum_f32": [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p],
-    "tagrec_row_add_at_f32": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
-    "tagrec_cor_fwd_f32": [c_void_p, c_int64, c_int64, c_int, c_int] + [c_void_p] * 7,
-    "tagrec_cor_bwd_f32": [c_void_p, c_int64, c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p],
-    "tagrec_probe_triad_f32": [c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int, c_void_p],
-    "tagrec_probe_read_f32": [c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_probe_gather_out_floats": [],
-    "tagrec_probe_clock": [c_int64, c_void_p, c_void_p],
-    "tagrec_probe_gather_rows_f32": [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p],
-    "tagrec_adam_advance": [c_void_p, c_void_p, c_float, c_float, c_float, c_void_p],
-    "tagrec_spmm_axpy_adam_graph_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p],
-    "tagrec_sum_n_f32": [c_void_p, c_void_p, c_int, c_int64, c_void_p],
-    "tagrec_layer_mean_rows_f32": [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p,
-                                   c_void_p, c_int, c_void_p],
-    "tagrec_adam_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int64,
-                        c_void_p],
-    "tagrec_adam_multi_f32": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int64, c_void_p],
-    "tagrec_adam_graph_f32": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float,
-                              c_void_p, c_void_p, c_void_p],
-}
+class Ptr:
+    """argtype of an untyped pointer parameter (void*, char*, a handle, a pointer to pointers): a GPU tensor of any
+    dtype, None (NULL), an address as a plain int, or a ctypes object (c_void_p, byref(...), an array) as it is."""
+    dtypes = None
+    _ctypes = (ctypes._SimpleCData, ctypes.Array, ctypes._Pointer, type(ctypes.byref(c_int())))
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            if cls.dtypes is not None and v.dtype not in cls.dtypes:
+                raise TypeError(f"expected a {' / '.join(map(str, cls.dtypes))} tensor, got {v.dtype}")
+            if not v.is_cuda:
+                raise TypeError(f"expected a GPU tensor (tagrec_amd has no CPU path), got one on {v.device}")
+            return c_void_p(v.data_ptr())       # never the bare int: ctypes would pass it as a C int
+        if v is None or isinstance(v, cls._ctypes):
+            return v                            # ctypes passes None as NULL
+        if type(v) is int:
+            return c_void_p(v)
+        raise TypeError(f"expected a tensor, None, an address or a ctypes object, got {type(v).__name__}")
+
+
+class F32Ptr(Ptr):
+    dtypes = (torch.float32,)
+
+
+class F64Ptr(Ptr):
+    dtypes = (torch.float64,)
+
+
+class I64Ptr(Ptr):
+    dtypes = (torch.int64,)
+
+
+class I32Ptr(Ptr):
+    dtypes = (torch.int32,)
+
+
+class U8Ptr(Ptr):                       # no torch.bool: no caller passes one
+    dtypes = (torch.uint8,)
+
+
+class U32Ptr(Ptr):                      # counters are allocated as int32
+    dtypes = (torch.int32, torch.uint32)
+
+
+class U64Ptr(Ptr):
+    dtypes = (torch.int64, torch.uint64)
+
+
+# C type of include/tagrec.h (const dropped, the stars joined to the base type) -> argtype
+_CTYPES = {"int": c_int, "int32_t": ctypes.c_int32, "int64_t": c_int64, "uint64_t": ctypes.c_uint64, "float": c_float,
+           "float*": F32Ptr, "double*": F64Ptr, "int64_t*": I64Ptr, "int32_t*": I32Ptr, "int*": I32Ptr, "uint8_t*": U8Ptr,
+           "unsigned*": U32Ptr, "uint64_t*": U64Ptr, "void*": Ptr, "char*": Ptr, "tagrec_graph*": Ptr,
+           "float**": Ptr, "int32_t**": Ptr, "int64_t**": Ptr, "tagrec_graph**": Ptr}
+
+
+def parse_header(text):
+    """{name: (restype, argtypes)} of every `ret tagrec_name(args);` in the text of a header.  Not a C parser: a type is
+    [const] word [const] stars, and whatever does not fit -- or a tagrec_ name the pattern did not reach -- is refused."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)            # comments, then preprocessor lines
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def ctype(decl, fn, ret=False):
+        m = re.fullmatch(r"\s*(\w+)\s*((?:\*\s*)*)(\w+)?\s*", re.sub(r"\bconst\b", " ", decl))
+        key = m and m.group(1) + "*" * m.group(2).count("*")
+        if ret and key == "char*":                      # the one pointer the library returns: tagrec_last_error's text
+            return c_char_p
+        if key not in _CTYPES or (ret and issubclass(_CTYPES[key], Ptr)):
+            raise TagrecError(f"include/tagrec.h: {fn}: no ctypes mapping for {' '.join(decl.split())!r}")
+        return _CTYPES[key]
+
+    protos = {}
+    for ret, fn, args in re.findall(r"([\w\s*]+?)\b(tagrec_\w+)\(([^()]*)\)\s*;", text):
+        protos[fn] = (ctype(ret, fn, True), [] if args.strip() == "void" else [ctype(a, fn) for a in args.split(",")])
+    known = set(protos) | {k.rstrip("*") for k in _CTYPES}
+    for m in re.finditer(r"\btagrec_\w+", text):
+        if m.group() not in known:
+            raise TagrecError(f"include/tagrec.h: {m.group()}: not a prototype this binding can read: "
+                              f"{' '.join(text[m.start():m.start() + 200].split(';')[0].split())!r}")
+    return protos
+
+
+_protos = None
+
+
+def _prototypes():
+    global _protos
+    if _protos is None:
+        if not os.path.exists(HEADER_PATH):
+            raise TagrecError(f"{HEADER_PATH} not found: the binding takes every signature from it")
+        with open(HEADER_PATH) as f:
+            _protos = parse_header(f.read())
+    return _protos
+
 
 _lib = None
 
@@ -278,12 +167,9 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  tagrec_amd has no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, (restype, argtypes) in _prototypes().items():
         fn = getattr(lib, name)       # AttributeError here = header and library disagree
-        fn.argtypes = argtypes
-        fn.restype = c_int64 if name.endswith(("_workspace", "_result", "_floats")) else c_int
-    lib.tagrec_last_error.argtypes = []
-    lib.tagrec_last_error.restype = c_char_p
+        fn.argtypes, fn.restype = argtypes, restype
     if lib.tagrec_abi_version() != ABI_VERSION:
         raise TagrecError(f"ABI mismatch: library {lib.tagrec_abi_version()}, host {ABI_VERSION}")
     _lib = lib
@@ -291,7 +177,7 @@ def load():
 
 
 def exported_symbols():
-    return list(_SIGNATURES) + ["tagrec_last_error"]
+    return list(_prototypes())
 
 
 def check(rc, what=""):
@@ -302,17 +188,16 @@ def check(rc, what=""):
 
 def stream_ptr():
     """torch's current HIP stream as the void* the ABI takes."""
-    import torch
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
+    """Device pointer of a tensor (None -> NULL), unchecked: for raw callers (tests, tools) and for the few places that
+    hand a buffer to a parameter of another pointee type on purpose.  The package otherwise passes the tensor itself."""
     return c_void_p(0 if t is None else t.data_ptr())
 
 
 def require_gpu_tensor(t, dtype, name):
-    import torch
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TagrecError(f"{name}: expected a GPU tensor (tagrec_amd has no CPU path), got {type(t).__name__}"
                           f"{'' if not isinstance(t, torch.Tensor) else ' on ' + str(t.device)}")

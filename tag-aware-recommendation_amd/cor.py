@@ -8,7 +8,7 @@ backward kernel as a device scalar.
 """
 import torch
 
-from ._lib import TagrecError, check, load, ptr, stream_ptr
+from ._lib import TagrecError, check, load, stream_ptr
 from .rowops import VEC_WIDTHS
 
 
@@ -35,8 +35,7 @@ def cor_fwd(x, K):
     sums = torch.empty(2 * K, dtype=torch.float64, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     coef = torch.empty(K, 3, dtype=torch.float32, device=dev)
-    check(load().tagrec_cor_fwd_f32(ptr(x), x.stride(0), n, D, K, ptr(rowsum), ptr(gsum), ptr(part), ptr(sums), ptr(loss),
-                                    ptr(coef), stream_ptr()), "cor_fwd")
+    check(load().tagrec_cor_fwd_f32(x, x.stride(0), n, D, K, rowsum, gsum, part, sums, loss, coef, stream_ptr()), "cor_fwd")
     return loss, (rowsum, gsum, coef)
 
 
@@ -47,8 +46,7 @@ def cor_bwd(x, K, saved, g, dx=None):
     rowsum, gsum, coef = saved
     if dx is None:
         dx = torch.empty(n, D, dtype=torch.float32, device=x.device)
-    check(load().tagrec_cor_bwd_f32(ptr(x), x.stride(0), n, D, K, ptr(rowsum), ptr(gsum), ptr(coef), ptr(g), ptr(dx),
-                                    dx.stride(0), stream_ptr()), "cor_bwd")
+    check(load().tagrec_cor_bwd_f32(x, x.stride(0), n, D, K, rowsum, gsum, coef, g, dx, dx.stride(0), stream_ptr()), "cor_bwd")
     return dx
 
 

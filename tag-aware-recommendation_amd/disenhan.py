@@ -92,9 +92,8 @@ class _EdgeSoftmax(torch.autograd.Function):
         sL, sR, r = sL.contiguous(), sR.contiguous(), r.contiguous()
         g = rel.rg.graph
         alpha = torch.empty(rel.nnz, dtype=torch.float32, device=sL.device)
-        _lib.check(_lib.load().tagrec_dh_edge_softmax_fwd_f32(_lib.ptr(g.rowptr), _lib.ptr(g.col), _lib.ptr(rel.mult), rel.shape[0],
-                                                              _lib.ptr(sL), _lib.ptr(sR), _lib.ptr(r), sL.shape[1],
-                                                              _lib.ptr(alpha), _lib.stream_ptr()), "dh_edge_softmax_fwd")
+        _lib.check(_lib.load().tagrec_dh_edge_softmax_fwd_f32(g.rowptr, g.col, rel.mult, rel.shape[0], sL, sR, r, sL.shape[1],
+                                                              alpha, _lib.stream_ptr()), "dh_edge_softmax_fwd")
         ctx.rel = rel
         ctx.save_for_backward(sL, sR, r, alpha)
         return alpha
@@ -113,11 +112,9 @@ def edge_softmax_bwd(rel, sL, sR, r, alpha, dalpha):
     scratch = torch.empty(rel.nnz, dtype=torch.float32, device=sL.device)
     dsL, dr = torch.empty_like(sL), torch.empty_like(r)
     dsR = torch.empty_like(sR)
-    _lib.check(_lib.load().tagrec_dh_edge_softmax_bwd_f32(_lib.ptr(g.rowptr), _lib.ptr(g.col), _lib.ptr(rel.mult), rel.shape[0],
-                                                          _lib.ptr(gt.rowptr), _lib.ptr(gt.col), _lib.ptr(rel.rg.perm), rel.shape[1],
-                                                          _lib.ptr(sL), _lib.ptr(sR), _lib.ptr(r), K, _lib.ptr(alpha),
-                                                          _lib.ptr(dalpha), _lib.ptr(scratch), _lib.ptr(dr), _lib.ptr(dsL),
-                                                          _lib.ptr(dsR), _lib.stream_ptr()), "dh_edge_softmax_bwd")
+    _lib.check(_lib.load().tagrec_dh_edge_softmax_bwd_f32(g.rowptr, g.col, rel.mult, rel.shape[0], gt.rowptr, gt.col, rel.rg.perm,
+                                                          rel.shape[1], sL, sR, r, K, alpha, dalpha, scratch, dr, dsL, dsR,
+                                                          _lib.stream_ptr()), "dh_edge_softmax_bwd")
     return dsL, dsR, dr
 
 
@@ -130,8 +127,7 @@ class _RelEpilogue(torch.autograd.Function):
         n, D = Y.shape
         Yl, Z = torch.empty_like(Y), torch.empty_like(Y)
         r = torch.empty(n, K, dtype=torch.float32, device=Y.device)
-        _lib.check(_lib.load().tagrec_dh_rel_epi_fwd_f32(_lib.ptr(Y), _lib.ptr(W), _lib.ptr(q), n, D, K, _lib.ptr(Yl), _lib.ptr(Z),
-                                                         _lib.ptr(r), _lib.stream_ptr()), "dh_rel_epi_fwd")
+        _lib.check(_lib.load().tagrec_dh_rel_epi_fwd_f32(Y, W, q, n, D, K, Yl, Z, r, _lib.stream_ptr()), "dh_rel_epi_fwd")
         ctx.K = K
         ctx.save_for_backward(Yl, Z, r, W, q)
         return Z, r
@@ -145,9 +141,8 @@ class _RelEpilogue(torch.autograd.Function):
         dZ = None if dZ is None else dZ.contiguous()
         dr = None if dr is None else dr.contiguous()
         dY, dZt, dsT = torch.empty_like(Yl), torch.empty_like(Yl), torch.empty_like(Yl)
-        _lib.check(_lib.load().tagrec_dh_rel_epi_bwd_f32(_lib.ptr(Yl), _lib.ptr(Z), _lib.ptr(r), _lib.ptr(dZ), _lib.ptr(dr),
-                                                         _lib.ptr(W), _lib.ptr(q), n, D, K, _lib.ptr(dY), _lib.ptr(dZt),
-                                                         _lib.ptr(dsT), _lib.stream_ptr()), "dh_rel_epi_bwd")
+        _lib.check(_lib.load().tagrec_dh_rel_epi_bwd_f32(Yl, Z, r, dZ, dr, W, q, n, D, K, dY, dZt, dsT, _lib.stream_ptr()),
+                   "dh_rel_epi_bwd")
         dW = torch.matmul(Yl.view(-1, dk).t(), dZt.view(-1, dk))
         dq = dsT.view(-1, dk).sum(0)
         return dY, dW, dq, None
@@ -162,8 +157,8 @@ class _Combine(torch.autograd.Function):
         n, D = ego.shape
         x, y = torch.empty_like(ego), torch.empty_like(ego)
         inv = torch.empty(n, K, dtype=torch.float32, device=ego.device)
-        _lib.check(_lib.load().tagrec_dh_combine_fwd_f32(_lib.ptr(ego), _lib.ptr(Z1), _lib.ptr(r1), _lib.ptr(Z2), _lib.ptr(r2), n, D, K,
-                                                         _lib.ptr(x), _lib.ptr(y), _lib.ptr(inv), _lib.stream_ptr()), "dh_combine_fwd")
+        _lib.check(_lib.load().tagrec_dh_combine_fwd_f32(ego, Z1, r1, Z2, r2, n, D, K, x, y, inv, _lib.stream_ptr()),
+                   "dh_combine_fwd")
         ctx.K = K
         ctx.save_for_backward(x, inv, Z1, r1, Z2, r2)
         return y
@@ -175,9 +170,8 @@ class _Combine(torch.autograd.Function):
         dy = dy.contiguous()
         dx, dZ1, dZ2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         dr1, dr2 = torch.empty_like(r1), torch.empty_like(r2)
-        _lib.check(_lib.load().tagrec_dh_combine_bwd_f32(_lib.ptr(x), _lib.ptr(inv), _lib.ptr(dy), _lib.ptr(Z1), _lib.ptr(r1), _lib.ptr(Z2),
-                                                         _lib.ptr(r2), n, D, ctx.K, _lib.ptr(dx), _lib.ptr(dZ1), _lib.ptr(dZ2),
-                                                         _lib.ptr(dr1), _lib.ptr(dr2), _lib.stream_ptr()), "dh_combine_bwd")
+        _lib.check(_lib.load().tagrec_dh_combine_bwd_f32(x, inv, dy, Z1, r1, Z2, r2, n, D, ctx.K, dx, dZ1, dZ2, dr1, dr2,
+                                                         _lib.stream_ptr()), "dh_combine_bwd")
         return dx, dZ1, dr1, dZ2, dr2, None
 
 

@@ -54,8 +54,8 @@ class HipOps:
 
     def mark_cols(self, g, rows, flags):
         rows = rows.contiguous()
-        _lib.check(_lib.load().tagrec_graph_mark_cols_u8(g.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(flags),
-                                                         _lib.stream_ptr()), "graph_mark_cols")
+        _lib.check(_lib.load().tagrec_graph_mark_cols_u8(g.handle, rows, rows.numel(), flags, _lib.stream_ptr()),
+                   "graph_mark_cols")
 
     def spmm_listed(self, g, rows, x, out):
         g.spmm_listed(rows, x, out)
@@ -130,25 +130,23 @@ class HipOps:
         g.spmm_flags(g_in, in_flags, in_count, out, out_flags, None, row_mask)
 
     def spmm_ss(self, g, x, y, ss):
-        g._call("spmm_ss", _lib.load().tagrec_spmm_ss_f32, g.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(ss), x.shape[1],
-                _lib.stream_ptr())
+        g._call("spmm_ss", _lib.load().tagrec_spmm_ss_f32, g.handle, x, y, ss, x.shape[1], _lib.stream_ptr())
 
     def spmm_normbwd_dot(self, g, g_in, x_raw, inv, dz, dot, s, out):
-        g._call("spmm_normbwd_dot", _lib.load().tagrec_spmm_normbwd_dot_f32, g.handle, _lib.ptr(g_in), _lib.ptr(x_raw),
-                _lib.ptr(inv), _lib.ptr(dz), _lib.ptr(dot), float(s), _lib.ptr(out), g_in.shape[1], _lib.stream_ptr())
+        g._call("spmm_normbwd_dot", _lib.load().tagrec_spmm_normbwd_dot_f32, g.handle, g_in, x_raw, inv, dz, dot, float(s), out,
+                g_in.shape[1], _lib.stream_ptr())
 
     def row_scale_acc(self, y, inv, s, acc):
-        _lib.check(_lib.load().tagrec_row_scale_acc_f32(_lib.ptr(y), _lib.ptr(inv), float(s), _lib.ptr(acc), y.shape[0],
-                                                        y.shape[1], _lib.stream_ptr()), "row_scale_acc")
+        _lib.check(_lib.load().tagrec_row_scale_acc_f32(y, inv, float(s), acc, y.shape[0], y.shape[1], _lib.stream_ptr()),
+                   "row_scale_acc")
 
     def row_dot(self, x, inv, dz, s, out):
-        _lib.check(_lib.load().tagrec_row_dot_f32(_lib.ptr(x), _lib.ptr(inv), _lib.ptr(dz), float(s), _lib.ptr(out),
-                                                  x.shape[0], x.shape[1], _lib.stream_ptr()), "row_dot")
+        _lib.check(_lib.load().tagrec_row_dot_f32(x, inv, dz, float(s), out, x.shape[0], x.shape[1], _lib.stream_ptr()),
+                   "row_dot")
 
     def rownorm_bwd_dot(self, x, inv, dz, dot, s, out):
-        _lib.check(_lib.load().tagrec_rownorm_bwd_dot_f32(_lib.ptr(x), _lib.ptr(inv), _lib.ptr(dz), _lib.ptr(dot), float(s),
-                                                          _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr()),
-                   "rownorm_bwd_dot")
+        _lib.check(_lib.load().tagrec_rownorm_bwd_dot_f32(x, inv, dz, dot, float(s), out, x.shape[0], x.shape[1],
+                                                          _lib.stream_ptr()), "rownorm_bwd_dot")
 
     # -- forward restricted to the rows the batch's loss depends on (see lightgcn.propagate_forward)
     restrict_forward = True
@@ -157,8 +155,7 @@ class HipOps:
         return g.mark_rows(rows, flags)
 
     def spmm_ss_rows(self, g, x, y, ss, mask):
-        g._call("spmm_ss_rows", _lib.load().tagrec_spmm_ss_rows_f32, g.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(ss), _lib.ptr(mask),
-                x.shape[1], _lib.stream_ptr())
+        g._call("spmm_ss_rows", _lib.load().tagrec_spmm_ss_rows_f32, g.handle, x, y, ss, mask, x.shape[1], _lib.stream_ptr())
 
     # -- row-sparse gradients (the batch gradient reaches a few rows per hop; see EpiArgs::in_flags in csrc/spmm.hip)
     sparse_backward = True
@@ -175,9 +172,8 @@ class HipOps:
             out_flags = torch.zeros(out.shape[0], dtype=torch.uint8, device=out.device)
             out.zero_()
         out_count = torch.zeros(1, dtype=torch.int32, device=out.device)
-        g._call("spmm_normbwd_dot", _lib.load().tagrec_spmm_normbwd_dot_sparse_f32, g.handle, _lib.ptr(g_in), _lib.ptr(fl[0]),
-                _lib.ptr(fl[1]), _lib.ptr(x_raw), _lib.ptr(inv), _lib.ptr(dz), _lib.ptr(dot), float(s), _lib.ptr(out),
-                _lib.ptr(out_flags), _lib.ptr(out_count), _lib.ptr(row_mask), g_in.shape[1], _lib.stream_ptr())
+        g._call("spmm_normbwd_dot", _lib.load().tagrec_spmm_normbwd_dot_sparse_f32, g.handle, g_in, fl[0], fl[1], x_raw, inv, dz,
+                dot, float(s), out, out_flags, out_count, row_mask, g_in.shape[1], _lib.stream_ptr())
         return out_flags, out_count
 
     def spmm_axpy_sparse(self, g, g_in, fl, b, s, out):

@@ -32,9 +32,8 @@ def fused_topk(user_table, item_table, users, train_ptr, train_items, k):
     users = users.to(U.device, torch.int64).contiguous()
     top = torch.empty(users.numel(), k, dtype=torch.int64, device=U.device)
     val = torch.empty(users.numel(), k, dtype=torch.float32, device=U.device)
-    _lib.check(_lib.load().tagrec_eval_topk_f32(_lib.ptr(U), _lib.ptr(I), I.shape[0], U.shape[1], _lib.ptr(users),
-                                                users.numel(), _lib.ptr(train_ptr), _lib.ptr(train_items), k,
-                                                _lib.ptr(top), _lib.ptr(val), _lib.stream_ptr()), "eval_topk")
+    _lib.check(_lib.load().tagrec_eval_topk_f32(U, I, I.shape[0], U.shape[1], users, users.numel(), train_ptr, train_items, k,
+                                                top, val, _lib.stream_ptr()), "eval_topk")
     return top, val
 
 
@@ -48,10 +47,9 @@ def fused_topk_auc(user_table, item_table, users, train_ptr, train_items, test_p
     top = torch.empty(users.numel(), k, dtype=torch.int64, device=U.device)
     val = torch.empty(users.numel(), k, dtype=torch.float32, device=U.device)
     num2, n_pos, n_neg = (torch.empty(users.numel(), dtype=torch.int64, device=U.device) for _ in range(3))
-    _lib.check(_lib.load().tagrec_eval_topk_auc_f32(
-        _lib.ptr(U), _lib.ptr(I), I.shape[0], U.shape[1], _lib.ptr(users), users.numel(), _lib.ptr(train_ptr),
-        _lib.ptr(train_items), _lib.ptr(test_ptr), _lib.ptr(test_items), k, _lib.ptr(top), _lib.ptr(val),
-        _lib.ptr(num2), _lib.ptr(n_pos), _lib.ptr(n_neg), _lib.stream_ptr()), "eval_topk_auc")
+    _lib.check(_lib.load().tagrec_eval_topk_auc_f32(U, I, I.shape[0], U.shape[1], users, users.numel(), train_ptr, train_items,
+                                                    test_ptr, test_items, k, top, val, num2, n_pos, n_neg, _lib.stream_ptr()),
+               "eval_topk_auc")
     return top, val, num2, n_pos, n_neg
 
 

@@ -220,12 +220,11 @@ class Graph:
                 off = (-self._ws.data_ptr()) % 256
                 self._ws_ptr = self._ws.data_ptr() + off
                 create = lib.tagrec_graph_create_ws_deferred if deferred else lib.tagrec_graph_create_ws
-                _lib.check(create(_lib.ctypes.byref(self._h), self.shape[0], self.shape[1], col.numel(), _lib.ptr(rowptr), _lib.ptr(col),
-                                  _lib.ptr(val), _lib.c_void_p(self._ws_ptr), nb, _lib.stream_ptr()), "graph_create_ws")
+                _lib.check(create(_lib.ctypes.byref(self._h), self.shape[0], self.shape[1], col.numel(), rowptr, col,
+                                  val, _lib.c_void_p(self._ws_ptr), nb, _lib.stream_ptr()), "graph_create_ws")
             else:
-                _lib.check(lib.tagrec_graph_create(_lib.ctypes.byref(self._h), self.shape[0], self.shape[1], col.numel(),
-                                                   _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(val), _lib.stream_ptr()),
-                           "graph_create")
+                _lib.check(lib.tagrec_graph_create(_lib.ctypes.byref(self._h), self.shape[0], self.shape[1], col.numel(), rowptr,
+                                                   col, val, _lib.stream_ptr()), "graph_create")
 
     def like(self, col, val, n_cols):
         """A second matrix over this graph's row pointer with its own columns / values; shares the long-row work list
@@ -245,11 +244,10 @@ class Graph:
             nb = lib.tagrec_graph_workspace(self.col.numel())
             g._ws = torch.empty(nb + 256, dtype=torch.uint8, device=self.val.device)
             g._ws_ptr = g._ws.data_ptr() + (-g._ws.data_ptr()) % 256
-            _lib.check(lib.tagrec_graph_create_like_ws(_lib.ctypes.byref(g._h), self._h, g.shape[1], _lib.ptr(col), _lib.ptr(val),
+            _lib.check(lib.tagrec_graph_create_like_ws(_lib.ctypes.byref(g._h), self._h, g.shape[1], col, val,
                                                        _lib.c_void_p(g._ws_ptr), nb), "graph_create_like_ws")
             return g
-        _lib.check(lib.tagrec_graph_create_like(_lib.ctypes.byref(g._h), self._h, g.shape[1], _lib.ptr(col),
-                                                _lib.ptr(val)), "graph_create_like")
+        _lib.check(lib.tagrec_graph_create_like(_lib.ctypes.byref(g._h), self._h, g.shape[1], col, val), "graph_create_like")
         return g
 
     @classmethod
@@ -363,7 +361,7 @@ class Graph:
             out = torch.empty(self.shape[0], D, dtype=torch.float32, device=X.device)
         self._chk_w(out, self.shape[0], D, "spmm out")
         self._chk_dev(X, "spmm X")
-        self._call("spmm", _lib.load().tagrec_spmm_f32, self._h, _lib.ptr(X), _lib.ptr(out), D, _lib.stream_ptr())
+        self._call("spmm", _lib.load().tagrec_spmm_f32, self._h, X, out, D, _lib.stream_ptr())
         return out
 
     def spmm_norm_acc(self, X, y_raw, inv_norm, acc, acc_scale, drop_p=0.0, seed=0):
@@ -375,11 +373,11 @@ class Graph:
         if inv_norm.numel() != self.shape[0] or acc.shape[1] != D or y_raw.shape[1] != D:
             raise _lib.TagrecError("spmm_norm_acc: shape mismatch")
         if drop_p > 0:
-            self._call("spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_drop_f32, self._h, _lib.ptr(X), _lib.ptr(y_raw),
-                       _lib.ptr(inv_norm), _lib.ptr(acc), float(acc_scale), float(drop_p), int(seed), D, _lib.stream_ptr())
+            self._call("spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_drop_f32, self._h, X, y_raw, inv_norm, acc,
+                       float(acc_scale), float(drop_p), int(seed), D, _lib.stream_ptr())
             return
-        self._call("spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_f32, self._h, _lib.ptr(X), _lib.ptr(y_raw),
-                   _lib.ptr(inv_norm), _lib.ptr(acc), float(acc_scale), D, _lib.stream_ptr())
+        self._call("spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_f32, self._h, X, y_raw, inv_norm, acc, float(acc_scale), D,
+                   _lib.stream_ptr())
 
     def mark_rows(self, rows, flags):
         """flags[c] = 1 for every column stored in `rows` (int64 node ids) and for the rows themselves."""
@@ -387,8 +385,8 @@ class Graph:
         if self.shape[0] != self.shape[1]:
             raise _lib.TagrecError("mark_rows: square adjacency expected (flags are indexed by node)")
         self._chk_vec(flags, self.shape[0], torch.uint8, "mark_rows flags")
-        _lib.check(_lib.load().tagrec_graph_mark_rows_u8(self._h, _lib.ptr(rows), rows.numel(), _lib.ptr(flags),
-                                                         _lib.stream_ptr()), "graph_mark_rows")
+        _lib.check(_lib.load().tagrec_graph_mark_rows_u8(self._h, rows, rows.numel(), flags, _lib.stream_ptr()),
+                   "graph_mark_rows")
         return flags
 
     def spmm_rows(self, X, out, row_mask):
@@ -396,8 +394,7 @@ class Graph:
         D = self._chk_x(X, self.shape[1], "spmm_rows X")
         self._chk_w(out, self.shape[0], D, "spmm_rows out")
         self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_rows row_mask")
-        self._call("spmm_rows", _lib.load().tagrec_spmm_rows_f32, self._h, _lib.ptr(X), _lib.ptr(out), _lib.ptr(row_mask), D,
-                   _lib.stream_ptr())
+        self._call("spmm_rows", _lib.load().tagrec_spmm_rows_f32, self._h, X, out, row_mask, D, _lib.stream_ptr())
         return out
 
     def spmm_listed(self, rows, X, out=None):
@@ -413,8 +410,8 @@ class Graph:
             return out
         ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), X.shape[1])
         ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
-        self._call("spmm_listed", lib.tagrec_spmm_listed_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
-                   _lib.ptr(out), X.shape[1], _lib.ptr(ws), ws_n, _lib.stream_ptr())
+        self._call("spmm_listed", lib.tagrec_spmm_listed_f32, self.handle, rows, rows.numel(), X, out, X.shape[1], ws, ws_n,
+                   _lib.stream_ptr())
         return out
 
     def spmm_norm_acc_rows(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, drop_p=0.0, seed=0):
@@ -423,9 +420,7 @@ class Graph:
         D = self._chk_x(X, self.shape[1], "spmm_norm_acc_rows X")
         self._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
         self._call("spmm_norm_acc_rows" if row_mask is not None else "spmm_norm_acc", _lib.load().tagrec_spmm_norm_acc_rows_f32,
-                   self._h, _lib.ptr(X), _lib.ptr(y_raw),
-                   _lib.ptr(inv_norm), _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), D,
-                   _lib.stream_ptr())
+                   self._h, X, y_raw, inv_norm, acc, float(acc_scale), row_mask, float(drop_p), int(seed), D, _lib.stream_ptr())
 
     def spmm_norm_acc_noise(self, X, y_raw, inv_norm, acc, acc_scale, row_mask, eps, seed, view, layer):
         """`spmm_norm_acc_rows` with the SimGCL perturbation in the epilogue: row r of the product becomes
@@ -435,9 +430,8 @@ class Graph:
         self._chk_dev(X, "spmm_norm_acc_noise X")
         self._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
         self._call("spmm_norm_acc_noise_rows" if row_mask is not None else "spmm_norm_acc_noise",
-                   _lib.load().tagrec_spmm_norm_acc_noise_f32, self._h, _lib.ptr(X), _lib.ptr(y_raw), _lib.ptr(inv_norm),
-                   _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(eps), int(seed), int(view), int(layer), D,
-                   _lib.stream_ptr())
+                   _lib.load().tagrec_spmm_norm_acc_noise_f32, self._h, X, y_raw, inv_norm, acc, float(acc_scale), row_mask,
+                   float(eps), int(seed), int(view), int(layer), D, _lib.stream_ptr())
 
     def _chk_norm_acc_rows(self, D, y_raw, inv_norm, acc, row_mask):
         self._chk_w(y_raw, self.shape[0], D, "spmm_norm_acc_rows y_raw")
@@ -471,12 +465,11 @@ class Graph:
             if self._chk_x(t, self.shape[0], "spmm_normbwd " + nm) != D:
                 raise _lib.TagrecError("spmm_normbwd: width mismatch on " + nm)
         if drop_p > 0:
-            self._call("spmm_normbwd", _lib.load().tagrec_spmm_normbwd_drop_f32, self._h, _lib.ptr(g_in), _lib.ptr(x_raw),
-                       _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p), int(seed), _lib.ptr(g_out), D,
-                       _lib.stream_ptr())
+            self._call("spmm_normbwd", _lib.load().tagrec_spmm_normbwd_drop_f32, self._h, g_in, x_raw, inv_norm, dz,
+                       float(d_scale), float(drop_p), int(seed), g_out, D, _lib.stream_ptr())
             return
-        self._call("spmm_normbwd", _lib.load().tagrec_spmm_normbwd_f32, self._h, _lib.ptr(g_in), _lib.ptr(x_raw),
-                   _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), _lib.ptr(g_out), D, _lib.stream_ptr())
+        self._call("spmm_normbwd", _lib.load().tagrec_spmm_normbwd_f32, self._h, g_in, x_raw, inv_norm, dz, float(d_scale), g_out,
+                   D, _lib.stream_ptr())
 
     def spmm_normbwd_sparse(self, g_in, in_flags, in_count, x_raw, inv_norm, dz, d_scale, g_out, out_flags, out_count,
                             drop_p=0.0, seed=0, row_mask=None, dz_flags=None):
@@ -486,10 +479,8 @@ class Graph:
         D = self._chk_x(g_in, self.shape[1], "spmm_normbwd_sparse g_in")
         self._chk_normbwd_sparse(D, in_flags, in_count, x_raw, inv_norm, dz, g_out, out_flags, out_count, row_mask, dz_flags)
         self._call("spmm_normbwd_rows" if row_mask is not None else "spmm_normbwd", _lib.load().tagrec_spmm_normbwd_sparse_f32,
-                   self._h, _lib.ptr(g_in), _lib.ptr(in_flags),
-                   _lib.ptr(in_count), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p),
-                   int(seed), _lib.ptr(g_out), _lib.ptr(out_flags), _lib.ptr(out_count), _lib.ptr(row_mask), _lib.ptr(dz_flags), D,
-                   _lib.stream_ptr())
+                   self._h, g_in, in_flags, in_count, x_raw, inv_norm, dz, float(d_scale), float(drop_p), int(seed), g_out,
+                   out_flags, out_count, row_mask, dz_flags, D, _lib.stream_ptr())
 
     BATCH_HOP_MAX_LISTED = 16384      # what tagrec_batch_hop_plan accepts
     BATCH_HOP_MAX_ROWS = 1 << 24
@@ -532,8 +523,8 @@ class Graph:
             self._hop_err = torch.zeros(1, dtype=torch.int32, device=self.device)
         off = (-buf.data_ptr()) % 256
         nbytes = buf.numel() - off
-        self._call("batch_hop_plan", _lib.load().tagrec_batch_hop_plan, self._h, _lib.ptr(rows), rows.numel(), int(capacity),
-                   _lib.c_void_p(buf.data_ptr() + off), nbytes, _lib.ptr(self._hop_err), _lib.stream_ptr())
+        self._call("batch_hop_plan", _lib.load().tagrec_batch_hop_plan, self._h, rows, rows.numel(), int(capacity),
+                   _lib.c_void_p(buf.data_ptr() + off), nbytes, self._hop_err, _lib.stream_ptr())
         return (buf, buf.data_ptr() + off, nbytes, rows.numel(), int(capacity))
 
     def batch_hop_rows(self, plan):
@@ -571,8 +562,8 @@ class Graph:
             raise _lib.TagrecError("batch_hop_normbwd: square matrix and one row_mask byte per row expected")
         _, ptr, nbytes, n_listed, capacity = plan
         self._call("batch_hop_normbwd", _lib.load().tagrec_batch_hop_normbwd_f32, self._h, _lib.c_void_p(ptr), nbytes, n_listed,
-                   capacity, _lib.ptr(g_in), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), _lib.ptr(g_out),
-                   _lib.ptr(out_flags), _lib.ptr(row_mask), _lib.ptr(dz_flags), D, _lib.stream_ptr())
+                   capacity, g_in, x_raw, inv_norm, dz, float(d_scale), g_out, out_flags, row_mask, dz_flags, D,
+                   _lib.stream_ptr())
 
     def spmm_axpy_sparse(self, g_in, in_flags, in_count, b, b_scale, g_out, row_mask=None, b_flags=None):
         """row_mask: rows whose byte is 0 are not touched (the caller knows their result and has written it).
@@ -580,8 +571,7 @@ class Graph:
         D = self._chk_x(g_in, self.shape[1], "spmm_axpy_sparse g_in")
         self._chk_axpy_sparse(D, in_flags, in_count, b, g_out, row_mask, b_flags)
         self._call("spmm_axpy_rows" if row_mask is not None else "spmm_axpy", _lib.load().tagrec_spmm_axpy_sparse_f32, self._h,
-                   _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(b), float(b_scale), _lib.ptr(g_out),
-                   _lib.ptr(row_mask), _lib.ptr(b_flags), D, _lib.stream_ptr())
+                   g_in, in_flags, in_count, b, float(b_scale), g_out, row_mask, b_flags, D, _lib.stream_ptr())
 
     def spmm_axpy_adam(self, g_in, in_flags, in_count, b, b_scale, b_flags, p, m, v, lr, betas, eps, step, dev=None):
         """The last hop with Adam folded in: row r of A g_in + b_scale b is the gradient of parameter row r and updates
@@ -596,14 +586,12 @@ class Graph:
         self._chk_count(in_count, "spmm_axpy_adam in_count")
         self._chk_vec(b_flags, self.shape[0], torch.uint8, "spmm_axpy_adam b_flags", optional=True)
         if dev is not None:
-            self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_adam_graph_f32, self._h, _lib.ptr(g_in), _lib.ptr(in_flags),
-                       _lib.ptr(in_count), _lib.ptr(b), float(b_scale), _lib.ptr(b_flags), _lib.ptr(p), _lib.ptr(m), _lib.ptr(v),
-                       float(lr), float(betas[0]), float(betas[1]), float(eps), _lib.ptr(dev[0]), _lib.ptr(dev[1]), D,
-                       _lib.stream_ptr())
+            self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_adam_graph_f32, self._h, g_in, in_flags, in_count, b,
+                       float(b_scale), b_flags, p, m, v, float(lr), float(betas[0]), float(betas[1]), float(eps), dev[0], dev[1],
+                       D, _lib.stream_ptr())
             return
-        self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_adam_f32, self._h, _lib.ptr(g_in), _lib.ptr(in_flags),
-                   _lib.ptr(in_count), _lib.ptr(b), float(b_scale), _lib.ptr(b_flags), _lib.ptr(p), _lib.ptr(m), _lib.ptr(v),
-                   float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), D, _lib.stream_ptr())
+        self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_adam_f32, self._h, g_in, in_flags, in_count, b, float(b_scale),
+                   b_flags, p, m, v, float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), D, _lib.stream_ptr())
 
     def spmm_flags(self, g_in, in_flags, in_count, g_out, out_flags, out_count=None, row_mask=None):
         """g_out = A @ g_in on a row-sparse operand (in_count None: flags always consulted), row flags of the result written
@@ -615,17 +603,15 @@ class Graph:
         self._chk_vec(out_flags, self.shape[0], torch.uint8, "spmm_flags out_flags", optional=True)
         self._chk_count(out_count, "spmm_flags out_count")
         self._chk_vec(row_mask, self.shape[0], torch.uint8, "spmm_flags row_mask", optional=True)
-        self._call("spmm_flags_rows" if row_mask is not None else "spmm_flags", _lib.load().tagrec_spmm_flags_f32, self._h,
-                   _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(g_out), _lib.ptr(out_flags),
-                   _lib.ptr(out_count), _lib.ptr(row_mask), D, _lib.stream_ptr())
+        self._call("spmm_flags_rows" if row_mask is not None else "spmm_flags", _lib.load().tagrec_spmm_flags_f32, self._h, g_in,
+                   in_flags, in_count, g_out, out_flags, out_count, row_mask, D, _lib.stream_ptr())
 
     def spmm_axpy(self, g_in, b, b_scale, g_out):
         D = self._chk_x(g_in, self.shape[1], "spmm_axpy g_in")
         for t, nm in ((b, "b"), (g_out, "g_out")):
             if self._chk_x(t, self.shape[0], "spmm_axpy " + nm) != D:
                 raise _lib.TagrecError("spmm_axpy: width mismatch on " + nm)
-        self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_f32, self._h, _lib.ptr(g_in), _lib.ptr(b),
-                   float(b_scale), _lib.ptr(g_out), D, _lib.stream_ptr())
+        self._call("spmm_axpy", _lib.load().tagrec_spmm_axpy_f32, self._h, g_in, b, float(b_scale), g_out, D, _lib.stream_ptr())
 
     # -- edge dropout inside the products ----------------------------------------------------------
     def edge_drop(self, p, seed):
@@ -636,7 +622,7 @@ class Graph:
     def edge_drop_mask(self, p, seed, transposed=False):
         """uint8 [nnz]: 1 where the stored entry (CSR order) survives the mask of (p, seed)."""
         mask = torch.empty(self.nnz, dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.load().tagrec_edge_drop_mask_u8(self._h, float(p), int(seed) & _U64, int(bool(transposed)), _lib.ptr(mask),
+        _lib.check(_lib.load().tagrec_edge_drop_mask_u8(self._h, float(p), int(seed) & _U64, int(bool(transposed)), mask,
                                                         _lib.stream_ptr()), "edge_drop_mask")
         return mask
 
@@ -706,8 +692,7 @@ class EdgeDropView:
             out = torch.empty(self.shape[0], D, dtype=torch.float32, device=X.device)
         self.base._chk_w(out, self.shape[0], D, "spmm out")
         self.base._chk_dev(X, "spmm X")
-        self.base._call("spmm", _lib.load().tagrec_spmm_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(out), *self._ed(), D,
-                        _lib.stream_ptr())
+        self.base._call("spmm", _lib.load().tagrec_spmm_edrop_f32, self.handle, X, out, *self._ed(), D, _lib.stream_ptr())
         return out
 
     def spmm_norm_acc(self, X, y_raw, inv_norm, acc, acc_scale, drop_p=0.0, seed=0):
@@ -717,9 +702,8 @@ class EdgeDropView:
         D = self._width(X, self.shape[1], "spmm_norm_acc_rows X")
         self.base._chk_norm_acc_rows(D, y_raw, inv_norm, acc, row_mask)
         self.base._call("spmm_norm_acc_rows" if row_mask is not None else "spmm_norm_acc",
-                        _lib.load().tagrec_spmm_norm_acc_rows_edrop_f32, self.handle, _lib.ptr(X), _lib.ptr(y_raw), _lib.ptr(inv_norm),
-                        _lib.ptr(acc), float(acc_scale), _lib.ptr(row_mask), float(drop_p), int(seed), *self._ed(), D,
-                        _lib.stream_ptr())
+                        _lib.load().tagrec_spmm_norm_acc_rows_edrop_f32, self.handle, X, y_raw, inv_norm, acc, float(acc_scale),
+                        row_mask, float(drop_p), int(seed), *self._ed(), D, _lib.stream_ptr())
 
     def spmm_listed(self, rows, X, out=None):
         rows = self.base._chk_rows(rows, "spmm_listed rows")
@@ -733,8 +717,8 @@ class EdgeDropView:
             return out
         ws_n = lib.tagrec_spmm_listed_workspace(rows.numel(), D)
         ws = torch.empty(max(ws_n, 1), dtype=torch.float32, device=X.device)
-        self.base._call("spmm_listed", lib.tagrec_spmm_listed_edrop_f32, self.handle, _lib.ptr(rows), rows.numel(), _lib.ptr(X),
-                        _lib.ptr(out), D, _lib.ptr(ws), ws_n, *self._ed(), _lib.stream_ptr())
+        self.base._call("spmm_listed", lib.tagrec_spmm_listed_edrop_f32, self.handle, rows, rows.numel(), X, out, D, ws, ws_n,
+                        *self._ed(), _lib.stream_ptr())
         return out
 
     def spmm_normbwd(self, g_in, x_raw, inv_norm, dz, d_scale, g_out, drop_p=0.0, seed=0):
@@ -745,10 +729,9 @@ class EdgeDropView:
         D = self._width(g_in, self.shape[1], "spmm_normbwd_sparse g_in")
         self.base._chk_normbwd_sparse(D, in_flags, in_count, x_raw, inv_norm, dz, g_out, out_flags, out_count, row_mask, dz_flags)
         self.base._call("spmm_normbwd_rows" if row_mask is not None else "spmm_normbwd",
-                        _lib.load().tagrec_spmm_normbwd_sparse_edrop_f32, self.handle, _lib.ptr(g_in), _lib.ptr(in_flags),
-                        _lib.ptr(in_count), _lib.ptr(x_raw), _lib.ptr(inv_norm), _lib.ptr(dz), float(d_scale), float(drop_p),
-                        int(seed), _lib.ptr(g_out), _lib.ptr(out_flags), _lib.ptr(out_count), _lib.ptr(row_mask),
-                        _lib.ptr(dz_flags), *self._ed(), D, _lib.stream_ptr())
+                        _lib.load().tagrec_spmm_normbwd_sparse_edrop_f32, self.handle, g_in, in_flags, in_count, x_raw, inv_norm, dz,
+                        float(d_scale), float(drop_p), int(seed), g_out, out_flags, out_count, row_mask, dz_flags, *self._ed(), D,
+                        _lib.stream_ptr())
 
     def spmm_axpy(self, g_in, b, b_scale, g_out):
         self.spmm_axpy_sparse(g_in, None, None, b, b_scale, g_out)
@@ -757,8 +740,8 @@ class EdgeDropView:
         D = self._width(g_in, self.shape[1], "spmm_axpy_sparse g_in")
         self.base._chk_axpy_sparse(D, in_flags, in_count, b, g_out, row_mask, b_flags)
         self.base._call("spmm_axpy_rows" if row_mask is not None else "spmm_axpy", _lib.load().tagrec_spmm_axpy_sparse_edrop_f32,
-                        self.handle, _lib.ptr(g_in), _lib.ptr(in_flags), _lib.ptr(in_count), _lib.ptr(b), float(b_scale),
-                        _lib.ptr(g_out), _lib.ptr(row_mask), _lib.ptr(b_flags), *self._ed(), D, _lib.stream_ptr())
+                        self.handle, g_in, in_flags, in_count, b, float(b_scale), g_out, row_mask, b_flags, *self._ed(), D,
+                        _lib.stream_ptr())
 
 
 def creat_adj(data, use_tag, norm_type, split_adj_k, device):

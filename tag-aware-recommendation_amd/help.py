@@ -383,9 +383,8 @@ class _TransTagLoss(torch.autograd.Function):
         dist = torch.empty(B, 2, dtype=torch.float32, device=Eu.device)
         partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=Eu.device)
         out = torch.empty(2, dtype=torch.float32, device=Eu.device)
-        _lib.check(_lib.load().tagrec_transtag_fwd_f32(_lib.ptr(Eu), _lib.ptr(Ei), _lib.ptr(Et), Eu.stride(0), D,
-                                                       _lib.ptr(quad), B, float(margin), _lib.ptr(dist), _lib.ptr(partials),
-                                                       _lib.ptr(out), _lib.stream_ptr()), "transtag_fwd")
+        _lib.check(_lib.load().tagrec_transtag_fwd_f32(Eu, Ei, Et, Eu.stride(0), D, quad, B, float(margin), dist, partials, out,
+                                                       _lib.stream_ptr()), "transtag_fwd")
         ctx.save_for_backward(Eu, Ei, Et, quad, dist)
         ctx.margin = float(margin)
         return out
@@ -395,10 +394,8 @@ class _TransTagLoss(torch.autograd.Function):
         Eu, Ei, Et, quad, dist = ctx.saved_tensors
         g = g.contiguous()
         dEu, dEi, dEt = torch.zeros_like(Eu), torch.zeros_like(Ei), torch.zeros_like(Et)
-        _lib.check(_lib.load().tagrec_transtag_bwd_f32(_lib.ptr(Eu), _lib.ptr(Ei), _lib.ptr(Et), Eu.stride(0), Eu.shape[1],
-                                                       _lib.ptr(quad), quad.shape[0], ctx.margin, _lib.ptr(dist),
-                                                       _lib.ptr(g), _lib.ptr(dEu), _lib.ptr(dEi), _lib.ptr(dEt),
-                                                       _lib.stream_ptr()), "transtag_bwd")
+        _lib.check(_lib.load().tagrec_transtag_bwd_f32(Eu, Ei, Et, Eu.stride(0), Eu.shape[1], quad, quad.shape[0], ctx.margin,
+                                                       dist, g, dEu, dEi, dEt, _lib.stream_ptr()), "transtag_bwd")
         return dEu, dEi, dEt, None, None
 
 
@@ -435,11 +432,10 @@ def message_drop(x, p, seed, out=None, rows=None):
     x = x.contiguous()
     out = torch.empty_like(x) if out is None else out
     if rows is not None:
-        _lib.check(_lib.load().tagrec_dropout_rows_f32(_lib.ptr(x), _lib.ptr(out), _lib.ptr(rows), x.shape[0], x.shape[1],
-                                                       float(p), int(seed), _lib.stream_ptr()), "dropout_rows")
+        _lib.check(_lib.load().tagrec_dropout_rows_f32(x, out, rows, x.shape[0], x.shape[1], float(p), int(seed),
+                                                       _lib.stream_ptr()), "dropout_rows")
         return out
-    _lib.check(_lib.load().tagrec_dropout_f32(_lib.ptr(x), _lib.ptr(out), x.numel(), float(p), int(seed), _lib.stream_ptr()),
-               "dropout")
+    _lib.check(_lib.load().tagrec_dropout_f32(x, out, x.numel(), float(p), int(seed), _lib.stream_ptr()), "dropout")
     return out
 
 

@@ -28,9 +28,8 @@ def dense_forward(nei, x, w1p, w2p, xp, inv, z_slot, ldz, row_mask=None):
     """z_slot None: the normalised slot is not written.  row_mask (uint8 per row): rows with a zero byte are neither read
     nor written."""
     n, din = x.shape
-    _lib.check(_lib.load().tagrec_ngcf_dense_fwd_rows_f32(_lib.ptr(nei), _lib.ptr(x), _lib.ptr(w1p), _lib.ptr(w2p), n, din,
-                                                          w1p.shape[1], _lib.ptr(xp), _lib.ptr(inv), _lib.ptr(z_slot), ldz,
-                                                          _lib.ptr(row_mask), _lib.stream_ptr()), "ngcf_dense_fwd")
+    _lib.check(_lib.load().tagrec_ngcf_dense_fwd_rows_f32(nei, x, w1p, w2p, n, din, w1p.shape[1], xp, inv, z_slot, ldz, row_mask,
+                                                          _lib.stream_ptr()), "ngcf_dense_fwd")
 
 
 def dense_backward(dxp, nei, x, w1p, w2p, norm=None, row_mask=None, dz_flags=None):
@@ -45,22 +44,18 @@ def dense_backward(dxp, nei, x, w1p, w2p, norm=None, row_mask=None, dz_flags=Non
     lib = _lib.load()
     if norm is not None:
         xp, inv, dz, ldz = norm
-        _lib.check(lib.tagrec_ngcf_dense_bwd_rows_f32(_lib.ptr(dxp), _lib.ptr(xp), _lib.ptr(inv), _lib.ptr(dz), ldz,
-                                                      _lib.ptr(dz_flags), _lib.ptr(nei), _lib.ptr(x), _lib.ptr(w1p), _lib.ptr(w2p),
-                                                      n, din, dout, _lib.ptr(d_nei), _lib.ptr(d_xd), _lib.ptr(dp1), _lib.ptr(dp2),
-                                                      _lib.ptr(row_mask), _lib.stream_ptr()), "ngcf_dense_bwd_norm")
+        _lib.check(lib.tagrec_ngcf_dense_bwd_rows_f32(dxp, xp, inv, dz, ldz, dz_flags, nei, x, w1p, w2p, n, din, dout, d_nei, d_xd,
+                                                      dp1, dp2, row_mask, _lib.stream_ptr()), "ngcf_dense_bwd_norm")
     else:
         if row_mask is not None:
             raise _lib.TagrecError("dense_backward: a row mask needs the fused normalize-backward form (norm=...)")
-        _lib.check(lib.tagrec_ngcf_dense_bwd_f32(_lib.ptr(dxp), _lib.ptr(nei), _lib.ptr(x), _lib.ptr(w1p), _lib.ptr(w2p), n,
-                                                 din, dout, _lib.ptr(d_nei), _lib.ptr(d_xd), _lib.ptr(dp1), _lib.ptr(dp2),
-                                                 _lib.stream_ptr()), "ngcf_dense_bwd")
+        _lib.check(lib.tagrec_ngcf_dense_bwd_f32(dxp, nei, x, w1p, w2p, n, din, dout, d_nei, d_xd, dp1, dp2, _lib.stream_ptr()),
+                   "ngcf_dense_bwd")
     ws_n = lib.tagrec_ngcf_wgrad_workspace(din, dout)
     ws = torch.empty(ws_n, dtype=torch.float32, device=x.device)
     dw1, dw2 = torch.empty_like(w1p), torch.empty_like(w2p)
-    _lib.check(lib.tagrec_ngcf_wgrad_rows_f32(_lib.ptr(nei), _lib.ptr(x), _lib.ptr(dp1), _lib.ptr(dp2), n, din, dout,
-                                              _lib.ptr(dw1), _lib.ptr(dw2), _lib.ptr(ws), ws_n, _lib.ptr(row_mask),
-                                              _lib.stream_ptr()), "ngcf_wgrad")
+    _lib.check(lib.tagrec_ngcf_wgrad_rows_f32(nei, x, dp1, dp2, n, din, dout, dw1, dw2, ws, ws_n, row_mask, _lib.stream_ptr()),
+               "ngcf_wgrad")
     return d_nei, d_xd, dw1, dw2
 
 

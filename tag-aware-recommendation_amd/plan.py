@@ -57,11 +57,11 @@ class RowPlan:
         all3 = (ctypes.c_int * 3)(*[1 if t in all_types else 0 for t in TYPES])
         s = _lib.stream_ptr()
         _lib.check(lib.tagrec_plan_mark_u8(n, idx_a, rows_a, stride_a, nrows_a, nsrc_a, k_a, type_a, all3, self._sizes3,
-                                           _lib.ptr(self.flags), _lib.ptr(self.counts), s), "plan_mark")
+                                           self.flags, self.counts, s), "plan_mark")
         rows_out = torch.empty(sum(self.sizes), dtype=torch.int64, device=self.device)
         pos_out = torch.empty(self.total, dtype=torch.int32, device=self.device)
-        _lib.check(lib.tagrec_plan_compact_i64(_lib.ptr(self.flags), self._sizes3, _lib.ptr(rows_out), _lib.ptr(pos_out),
-                                               _lib.ptr(self.counts), _lib.ptr(self.ws), self.ws_ints, s), "plan_compact")
+        _lib.check(lib.tagrec_plan_compact_i64(self.flags, self._sizes3, rows_out, pos_out, self.counts, self.ws, self.ws_ints, s),
+                   "plan_compact")
         c = self.counts.tolist()                     # the level's one host read
         if c[3]:
             raise IndexError(f"row plan: {c[3]} node ids out of range in the batch / the neighbour tables")
@@ -77,8 +77,7 @@ def lookup(pos, rows, *, stride=1, n=None, out=None, out_stride=1):
         n = rows.numel()
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=pos.device)
-    rp = rows.data_ptr() if isinstance(rows, torch.Tensor) else int(rows)
-    op = out.data_ptr() if isinstance(out, torch.Tensor) else int(out)
-    _lib.check(_lib.load().tagrec_plan_lookup_i64(_lib.ptr(pos), ctypes.c_void_p(rp), stride, n, ctypes.c_void_p(op), out_stride,
-                                                  _lib.stream_ptr()), "plan_lookup")
+    rp = rows if isinstance(rows, torch.Tensor) else int(rows)
+    op = out if isinstance(out, torch.Tensor) else int(out)
+    _lib.check(_lib.load().tagrec_plan_lookup_i64(pos, rp, stride, n, op, out_stride, _lib.stream_ptr()), "plan_lookup")
     return out

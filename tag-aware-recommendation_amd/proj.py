@@ -28,8 +28,7 @@ def tall_mm(X1, W1, out, *, X2=None, sel=None, W2=None, w_split=0, transposed=Fa
     K = X1.shape[1] * (2 if X2 is not None else 1)
     NO = out.shape[1] * (2 if out2 is not None else 1)
     _, sk, sc = _strides(W1, transposed)
-    _lib.check(_lib.load().tagrec_tall_mm_f32(_lib.ptr(X1), _lib.ptr(X2), _lib.ptr(sel), n, K, NO, _lib.ptr(W1), _lib.ptr(W2), sk, sc,
-                                              w_split, _lib.ptr(b1), _lib.ptr(b2), _lib.ptr(out), _lib.ptr(out2),
+    _lib.check(_lib.load().tagrec_tall_mm_f32(X1, X2, sel, n, K, NO, W1, W2, sk, sc, w_split, b1, b2, out, out2,
                                               1 if accumulate else 0, _lib.stream_ptr()), "tall_mm")
     return out
 
@@ -40,8 +39,8 @@ def tall_mm_adam(X, W, g_in, param, m, v, lr, betas, eps, step, *, transposed=Fa
     n, K = X.shape
     NO = param.shape[1]
     _, sk, sc = _strides(W, transposed)
-    _lib.check(_lib.load().tagrec_tall_mm_adam_f32(_lib.ptr(X), n, K, NO, _lib.ptr(W), sk, sc, _lib.ptr(g_in), _lib.ptr(param), _lib.ptr(m),
-                                                   _lib.ptr(v), lr, betas[0], betas[1], eps, step, _lib.stream_ptr()), "tall_mm_adam")
+    _lib.check(_lib.load().tagrec_tall_mm_adam_f32(X, n, K, NO, W, sk, sc, g_in, param, m, v, lr, betas[0], betas[1], eps, step,
+                                                   _lib.stream_ptr()), "tall_mm_adam")
 
 
 def tall_wgrad(X, dY1, dY2=None, *, dW=None, db1=None, db2=None, acc_w=False, acc_b=False):
@@ -53,8 +52,8 @@ def tall_wgrad(X, dY1, dY2=None, *, dW=None, db1=None, db2=None, acc_w=False, ac
         dW = torch.empty(KI, NO, dtype=torch.float32, device=X.device)
     ws_n = lib.tagrec_tall_wgrad_workspace(KI, NO)
     ws = torch.empty(ws_n, dtype=torch.float32, device=X.device)
-    _lib.check(lib.tagrec_tall_wgrad_f32(_lib.ptr(X), _lib.ptr(dY1), _lib.ptr(dY2), n, KI, NO, _lib.ptr(dW), _lib.ptr(db1), _lib.ptr(db2),
-                                         1 if acc_w else 0, 1 if acc_b else 0, _lib.ptr(ws), ws_n, _lib.stream_ptr()), "tall_wgrad")
+    _lib.check(lib.tagrec_tall_wgrad_f32(X, dY1, dY2, n, KI, NO, dW, db1, db2, 1 if acc_w else 0, 1 if acc_b else 0, ws, ws_n,
+                                         _lib.stream_ptr()), "tall_wgrad")
     return dW
 
 
@@ -64,15 +63,14 @@ def small_mm(A, B, out=None, accumulate=False):
     N = B.shape[1]
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=A.device)
-    _lib.check(_lib.load().tagrec_small_mm_f32(_lib.ptr(A), _lib.ptr(B), _lib.ptr(out), M, N, K, A.stride(0), A.stride(1), B.stride(0),
-                                               B.stride(1), 1 if accumulate else 0, _lib.stream_ptr()), "small_mm")
+    _lib.check(_lib.load().tagrec_small_mm_f32(A, B, out, M, N, K, A.stride(0), A.stride(1), B.stride(0), B.stride(1),
+                                               1 if accumulate else 0, _lib.stream_ptr()), "small_mm")
     return out
 
 
 def row_add_at(dst, pos, src):
     """dst[pos[i]] += src[i] for DISTINCT positions (int64)."""
-    _lib.check(_lib.load().tagrec_row_add_at_f32(_lib.ptr(dst), _lib.ptr(pos), _lib.ptr(src), src.shape[0], src.shape[1],
-                                                 _lib.stream_ptr()), "row_add_at")
+    _lib.check(_lib.load().tagrec_row_add_at_f32(dst, pos, src, src.shape[0], src.shape[1], _lib.stream_ptr()), "row_add_at")
     return dst
 
 
@@ -83,6 +81,5 @@ def masked_colsum(d_out, out):
     res = torch.empty(D, dtype=torch.float32, device=d_out.device)
     ws_n = lib.tagrec_masked_colsum_workspace(D)
     ws = torch.empty(ws_n, dtype=torch.float32, device=d_out.device)
-    _lib.check(lib.tagrec_masked_colsum_f32(_lib.ptr(d_out), _lib.ptr(out), n, D, _lib.ptr(res), _lib.ptr(ws), ws_n, _lib.stream_ptr()),
-               "masked_colsum")
+    _lib.check(lib.tagrec_masked_colsum_f32(d_out, out, n, D, res, ws, ws_n, _lib.stream_ptr()), "masked_colsum")
     return res

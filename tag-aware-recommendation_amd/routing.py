@@ -52,20 +52,20 @@ class RoutingGraph:
     # ---- kernels ------------------------------------------------------------------------------------------
     def softmax(self, logits):
         w = torch.empty_like(logits)
-        _lib.check(_lib.load().tagrec_route_softmax_f32(_lib.ptr(logits), _lib.ptr(w), logits.shape[0], logits.shape[1],
-                                                        _lib.stream_ptr()), "route_softmax")
+        _lib.check(_lib.load().tagrec_route_softmax_f32(logits, w, logits.shape[0], logits.shape[1], _lib.stream_ptr()),
+                   "route_softmax")
         return w
 
     def rowsum_rsqrt(self, w):
         d = torch.empty(self.n, w.shape[1], dtype=torch.float32, device=self.device)
-        self.graph._call("route_rowsum_rsqrt", _lib.load().tagrec_route_rowsum_rsqrt_f32, self.graph.handle, _lib.ptr(w),
-                         w.shape[1], _lib.ptr(d), _lib.stream_ptr())
+        self.graph._call("route_rowsum_rsqrt", _lib.load().tagrec_route_rowsum_rsqrt_f32, self.graph.handle, w, w.shape[1], d,
+                         _lib.stream_ptr())
         return d
 
     def permute(self, w):
         wt = torch.empty_like(w)
-        _lib.check(_lib.load().tagrec_route_permute_f32(_lib.ptr(w), _lib.ptr(self.perm), _lib.ptr(wt), w.shape[0], w.shape[1],
-                                                        _lib.stream_ptr()), "route_permute")
+        _lib.check(_lib.load().tagrec_route_permute_f32(w, self.perm, wt, w.shape[0], w.shape[1], _lib.stream_ptr()),
+                   "route_permute")
         return wt
 
     def spmm(self, w, x, post=None, self_add=None, b=None, b_scale=0.0, raw=True, normed=False, transposed=False,
@@ -89,16 +89,14 @@ class RoutingGraph:
         if sparse_x:
             flags, count = rowops.row_flags(x)
         name = "route_spmm" if (row_mask is None and not sparse_x) else "route_spmm_restricted"     # timing key
-        self.graph._call(name, _lib.load().tagrec_route_spmm_ex_f32, g.handle, _lib.ptr(w), K, _lib.ptr(x),
-                         _lib.ptr(post), _lib.ptr(self_add), _lib.ptr(b), float(b_scale), _lib.ptr(y), _lib.ptr(yn),
-                         _lib.ptr(inv), _lib.ptr(row_mask), _lib.ptr(flags), _lib.ptr(count), D, _lib.stream_ptr())
+        self.graph._call(name, _lib.load().tagrec_route_spmm_ex_f32, g.handle, w, K, x, post, self_add, b, float(b_scale), y, yn,
+                         inv, row_mask, flags, count, D, _lib.stream_ptr())
         return y, yn, inv
 
     def score(self, h, t, logits, accumulate, row_mask=None):
         """row_mask: only the entries of rows with a non-zero byte are scored (the others keep their logits)."""
         self.graph._call("route_score" if row_mask is None else "route_score_rows", _lib.load().tagrec_route_score_rows_f32,
-                         self.graph.handle, _lib.ptr(h), _lib.ptr(t),
-                         _lib.ptr(logits), logits.shape[1], int(bool(accumulate)), _lib.ptr(row_mask), h.shape[1],
+                         self.graph.handle, h, t, logits, logits.shape[1], int(bool(accumulate)), row_mask, h.shape[1],
                          _lib.stream_ptr())
 
     def loss_row_mask(self, loss_rows):
@@ -110,14 +108,12 @@ class RoutingGraph:
 
     def row_softmax(self, logits):
         a = torch.empty_like(logits)
-        _lib.check(_lib.load().tagrec_row_softmax_fwd_f32(self.graph.handle, _lib.ptr(logits), _lib.ptr(a), _lib.stream_ptr()),
-                   "row_softmax_fwd")
+        _lib.check(_lib.load().tagrec_row_softmax_fwd_f32(self.graph.handle, logits, a, _lib.stream_ptr()), "row_softmax_fwd")
         return a
 
     def row_softmax_bwd(self, a, da):
         dl = torch.empty_like(a)
-        _lib.check(_lib.load().tagrec_row_softmax_bwd_f32(self.graph.handle, _lib.ptr(a), _lib.ptr(da), _lib.ptr(dl),
-                                                          _lib.stream_ptr()), "row_softmax_bwd")
+        _lib.check(_lib.load().tagrec_row_softmax_bwd_f32(self.graph.handle, a, da, dl, _lib.stream_ptr()), "row_softmax_bwd")
         return dl
 
 
@@ -192,23 +188,23 @@ def valued_spmm(a, X, rg):
 
 def slice_scale(x, scale):
     y = torch.empty_like(x)
-    _lib.check(_lib.load().tagrec_slice_scale_f32(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(y), x.shape[0], x.shape[1],
-                                                  scale.shape[1], _lib.stream_ptr()), "slice_scale")
+    _lib.check(_lib.load().tagrec_slice_scale_f32(x, scale, y, x.shape[0], x.shape[1], scale.shape[1], _lib.stream_ptr()),
+               "slice_scale")
     return y
 
 
 def slice_norm_fwd(x, K, tanh=False, want_inv=True):
     y = torch.empty_like(x)
     inv = torch.empty(x.shape[0], K, dtype=torch.float32, device=x.device) if want_inv else None
-    _lib.check(_lib.load().tagrec_slice_norm_fwd_f32(_lib.ptr(x), _lib.ptr(y), _lib.ptr(inv), x.shape[0], x.shape[1], K,
-                                                     int(bool(tanh)), _lib.stream_ptr()), "slice_norm_fwd")
+    _lib.check(_lib.load().tagrec_slice_norm_fwd_f32(x, y, inv, x.shape[0], x.shape[1], K, int(bool(tanh)), _lib.stream_ptr()),
+               "slice_norm_fwd")
     return y, inv
 
 
 def slice_norm_bwd(x_raw, inv, dz):
     dx = torch.empty_like(x_raw)
-    _lib.check(_lib.load().tagrec_slice_norm_bwd_f32(_lib.ptr(x_raw), _lib.ptr(inv), _lib.ptr(dz), _lib.ptr(dx), x_raw.shape[0],
-                                                     x_raw.shape[1], inv.shape[1], _lib.stream_ptr()), "slice_norm_bwd")
+    _lib.check(_lib.load().tagrec_slice_norm_bwd_f32(x_raw, inv, dz, dx, x_raw.shape[0], x_raw.shape[1], inv.shape[1],
+                                                     _lib.stream_ptr()), "slice_norm_bwd")
     return dx
 
 

@@ -7,7 +7,7 @@ stays referenced until the launch has been enqueued.
 import torch
 
 from . import _lib
-from ._lib import check, load, ptr, stream_ptr
+from ._lib import check, load, stream_ptr
 
 VEC_WIDTHS = (8, 16, 32, 64, 128, 256)      # row widths the vector (row-sparse / row-masked) kernels are built for
 
@@ -19,7 +19,7 @@ def rownorm_fwd(x, z=None, inv=None):
         z = torch.empty(n, D, dtype=torch.float32, device=x.device)
     if inv is None:
         inv = torch.empty(n, dtype=torch.float32, device=x.device)
-    check(load().tagrec_rownorm_fwd_f32(ptr(x), ptr(z), z.stride(0), ptr(inv), n, D, stream_ptr()), "rownorm_fwd")
+    check(load().tagrec_rownorm_fwd_f32(x, z, z.stride(0), inv, n, D, stream_ptr()), "rownorm_fwd")
     return z, inv
 
 
@@ -39,8 +39,8 @@ def noise_rownorm_fwd(y, node_ids, eps, seed, view, layer, z=None, inv=None):
         z = torch.empty(T, D, dtype=torch.float32, device=y.device)
     if inv is None:
         inv = torch.empty(T, dtype=torch.float32, device=y.device)
-    check(load().tagrec_noise_rownorm_fwd_f32(ptr(y), ptr(node_ids), T, float(eps), int(seed), int(view), int(layer), ptr(z),
-                                              z.stride(0) if T > 1 else D, ptr(inv), D, stream_ptr()), "noise_rownorm_fwd")
+    check(load().tagrec_noise_rownorm_fwd_f32(y, node_ids, T, float(eps), int(seed), int(view), int(layer), z,
+                                              z.stride(0) if T > 1 else D, inv, D, stream_ptr()), "noise_rownorm_fwd")
     return z, inv
 
 
@@ -55,15 +55,14 @@ def noise_dir(node_ids, D, seed, view, layer, device=None):
         T, ids, device = node_ids.numel(), node_ids, node_ids.device
         _node_ids("noise_dir", ids, T, device)
     out = torch.empty(T, D, dtype=torch.float32, device=device)
-    check(load().tagrec_noise_dir_f32(ptr(out), ptr(ids), T, int(seed), int(view), int(layer), D, stream_ptr()), "noise_dir")
+    check(load().tagrec_noise_dir_f32(out, ids, T, int(seed), int(view), int(layer), D, stream_ptr()), "noise_dir")
     return out
 
 
 def rownorm_bwd(x_raw, inv, dz, s, out, accumulate=False):
     """out (+)= normalize-backward(x_raw, inv, s * dz); dz may be a strided slot view."""
     n, D = x_raw.shape
-    check(load().tagrec_rownorm_bwd_f32(ptr(x_raw), ptr(inv), ptr(dz), dz.stride(0), s, ptr(out), int(accumulate), n, D,
-                                        stream_ptr()), "rownorm_bwd")
+    check(load().tagrec_rownorm_bwd_f32(x_raw, inv, dz, dz.stride(0), s, out, int(accumulate), n, D, stream_ptr()), "rownorm_bwd")
     return out
 
 
@@ -83,8 +82,8 @@ def layer_mean_rows(x0, rows, raws, invs, z_top, s, want_ego=True):
     ego_b = torch.empty(T, D, dtype=torch.float32, device=x0.device) if want_ego else None
     ys = (_lib.c_void_p * max(len(raws), 1))(*[y.data_ptr() for y in raws])
     vs = (_lib.c_void_p * max(len(invs), 1))(*[v.data_ptr() for v in invs])
-    check(load().tagrec_layer_mean_rows_f32(ptr(x0), ptr(rows), T, n, ys, vs, len(raws), ptr(z_top), float(s), ptr(out_b),
-                                            ptr(ego_b), D, stream_ptr()), "layer_mean_rows")
+    check(load().tagrec_layer_mean_rows_f32(x0, rows, T, n, ys, vs, len(raws), z_top, float(s), out_b, ego_b, D, stream_ptr()),
+          "layer_mean_rows")
     return out_b, ego_b
 
 
@@ -100,8 +99,8 @@ def rownorm_bwd_flags(x_raw, inv, dz, s, out, flags=None, count=None):
     """`rownorm_bwd` that also writes which rows of `out` hold a non-zero and how many -> (flags, count)."""
     n, D = x_raw.shape
     flags, count = _flags_count(n, out.device, flags, count)
-    check(load().tagrec_rownorm_bwd_flags_f32(ptr(x_raw), ptr(inv), ptr(dz), dz.stride(0), s, ptr(out), 0, n, D, ptr(flags),
-                                              ptr(count), stream_ptr()), "rownorm_bwd_flags")
+    check(load().tagrec_rownorm_bwd_flags_f32(x_raw, inv, dz, dz.stride(0), s, out, 0, n, D, flags, count, stream_ptr()),
+          "rownorm_bwd_flags")
     return flags, count
 
 
@@ -109,7 +108,7 @@ def row_flags(x, flags=None, count=None):
     """flags[r] = row r of x holds a non-zero, count = number of such rows -> (flags, count)."""
     n, D = x.shape
     flags, count = _flags_count(n, x.device, flags, count)
-    check(load().tagrec_row_flags_f32(ptr(x), n, D, ptr(flags), ptr(count), stream_ptr()), "row_flags")
+    check(load().tagrec_row_flags_f32(x, n, D, flags, count, stream_ptr()), "row_flags")
     return flags, count
 
 
@@ -146,8 +145,8 @@ def bpr_fwd(U, I, Ureg, Ireg, trip, loss_kind):
     res = torch.empty(2, dtype=torch.float32, device=U.device)
     ld, D = _pair_ld("bpr_fwd", ("U", "I"), U, I)
     ldreg, dreg = _pair_ld("bpr_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
-    check(load().tagrec_bpr_fwd_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
-                                    loss_kind, ptr(coef), ptr(partials), ptr(res), stream_ptr()), "bpr_fwd")
+    check(load().tagrec_bpr_fwd_f32(U, I, ld, D, Ureg, Ireg, ldreg, dreg, trip, B, loss_kind, coef, partials, res, stream_ptr()),
+          "bpr_fwd")
     return res, coef
 
 
@@ -158,8 +157,7 @@ def bpr_bwd(U, I, Ureg, Ireg, trip, coef, g, dU, dI, dUreg, dIreg, what="bpr_bwd
     g = None if g is None else g.contiguous()
     ld, D = _pair_ld(what, ("U", "I"), U, I, (dU, dI))
     ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
-    check(load().tagrec_bpr_bwd_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip),
-                                    trip.shape[0], ptr(coef), ptr(g), 1.0, ptr(dU), ptr(dI), ptr(dUreg), ptr(dIreg),
+    check(load().tagrec_bpr_bwd_f32(U, I, ld, D, Ureg, Ireg, ldreg, dreg, trip, trip.shape[0], coef, g, 1.0, dU, dI, dUreg, dIreg,
                                     stream_ptr()), what)
 
 
@@ -169,8 +167,7 @@ def bpr_dots(U, I, Ureg, Ireg, trip):
     dots = torch.empty(B, 3, dtype=torch.float32, device=U.device)
     ld, D = _pair_ld("bpr_dots", ("U", "I"), U, I)
     ldreg, dreg = _pair_ld("bpr_dots", ("Ureg", "Ireg"), Ureg, Ireg)
-    check(load().tagrec_bpr_dots_f32(ptr(U), ptr(I), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, ptr(trip), B,
-                                     ptr(dots), stream_ptr()), "bpr_dots")
+    check(load().tagrec_bpr_dots_f32(U, I, ld, D, Ureg, Ireg, ldreg, dreg, trip, B, dots, stream_ptr()), "bpr_dots")
     return dots
 
 
@@ -220,8 +217,8 @@ def rank_fwd(Ub, Ib, Ureg, Ireg, loss_kind, temperature=1.0):
     coef = torch.empty(B, K + 1, dtype=torch.float32, device=Ub.device)
     partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=Ub.device)     # two floats per launched block
     res = torch.empty(2, dtype=torch.float32, device=Ub.device)
-    check(load().tagrec_rank_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, K, loss_kind,
-                                     float(temperature), ptr(coef), ptr(partials), ptr(res), stream_ptr()), "rank_fwd")
+    check(load().tagrec_rank_fwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, K, loss_kind, float(temperature), coef, partials,
+                                     res, stream_ptr()), "rank_fwd")
     return res, coef
 
 
@@ -239,8 +236,8 @@ def rank_bwd(Ub, Ib, Ureg, Ireg, coef, g, dUb, dIb, dUreg, dIreg, what="rank_bwd
     for nm, t, n in (("dUb", dUb, B), ("dIb", dIb, (1 + K) * B), ("dUreg", dUreg, B), ("dIreg", dIreg, (1 + K) * B)):
         if t is not None and t.shape[0] != n:
             raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {n} rows")
-    check(load().tagrec_rank_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, K, ptr(coef), ptr(g),
-                                     ptr(dUb), ptr(dIb), ptr(dUreg), ptr(dIreg), stream_ptr()), what)
+    check(load().tagrec_rank_bwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, K, coef, g, dUb, dIb, dUreg, dIreg, stream_ptr()),
+          what)
 
 
 # ---- in-batch sampled softmax on compact rows: the fused B x B loss (csrc/inbatch.hip) ----
@@ -275,9 +272,8 @@ def inbatch_fwd(Ub, Ib, Ureg, Ireg, temperature, uid=None, iid=None, col_bias=No
     lse = torch.empty(B, dtype=torch.float32, device=Ub.device)
     partials = torch.empty(2 * max(1, (B + INBATCH_TILE - 1) // INBATCH_TILE), dtype=torch.float32, device=Ub.device)
     res = torch.empty(2, dtype=torch.float32, device=Ub.device)
-    check(load().tagrec_inbatch_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(uid), ptr(iid), ptr(col_bias), ptr(Ureg), ptr(Ireg), ldreg,
-                                        dreg, B, float(temperature), ptr(lse), ptr(partials), ptr(res), stream_ptr()),
-          "inbatch_fwd")
+    check(load().tagrec_inbatch_fwd_f32(Ub, Ib, ld, D, uid, iid, col_bias, Ureg, Ireg, ldreg, dreg, B, float(temperature), lse,
+                                        partials, res, stream_ptr()), "inbatch_fwd")
     return res, lse
 
 
@@ -295,9 +291,8 @@ def inbatch_bwd(Ub, Ib, Ureg, Ireg, temperature, lse, g, dUb, dIb, dUreg, dIreg,
     for nm, t in (("dUb", dUb), ("dIb", dIb), ("dUreg", dUreg), ("dIreg", dIreg)):
         if t is not None and t.shape[0] != B:
             raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {B} rows")
-    check(load().tagrec_inbatch_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(uid), ptr(iid), ptr(col_bias), ptr(Ureg), ptr(Ireg), ldreg,
-                                        dreg, B, float(temperature), ptr(lse), ptr(g), ptr(dUb), ptr(dIb), ptr(dUreg),
-                                        ptr(dIreg), stream_ptr()), what)
+    check(load().tagrec_inbatch_bwd_f32(Ub, Ib, ld, D, uid, iid, col_bias, Ureg, Ireg, ldreg, dreg, B, float(temperature), lse, g,
+                                        dUb, dIb, dUreg, dIreg, stream_ptr()), what)
 
 
 # ---- catalogue softmax: the fused rectangular B x N softmax cross-entropy (csrc/catsoftmax.hip) ----
@@ -378,9 +373,9 @@ def catsoftmax_fwd(Q, T, target, temperature, qrow=None, Qreg=None, Treg=None, n
     B, N, D, ldreg, dreg, workspace = _catsoftmax_args("catsoftmax_fwd", Q, T, target, qrow, Qreg, Treg, n_split, workspace)
     small = torch.empty(2 * B + 2, dtype=torch.float32, device=Q.device)         # lse | zt | res
     lse, zt, res = small[:B], small[B:2 * B], small[2 * B:]
-    check(load().tagrec_catsoftmax_fwd_f32(ptr(Q), _row_ld(Q), ptr(qrow), ptr(T), _row_ld(T), N, D, ptr(target), ptr(Qreg), ptr(Treg),
-                                           ldreg, dreg, B, float(temperature), n_split, ptr(workspace), workspace.numel(), ptr(lse),
-                                           ptr(zt), ptr(res), stream_ptr()), "catsoftmax_fwd")
+    check(load().tagrec_catsoftmax_fwd_f32(Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B,
+                                           float(temperature), n_split, workspace, workspace.numel(), lse, zt, res, stream_ptr()),
+          "catsoftmax_fwd")
     return res, lse, zt
 
 
@@ -411,9 +406,9 @@ def catsoftmax_bwd(Q, T, target, temperature, lse, g, dT, dQ=None, qrow=None, Qr
     for nm, t in (("dQreg", dQreg), ("dTreg", dTreg)):
         if t is not None and (t.shape != (B, dreg) or t.dtype != torch.float32 or not t.is_contiguous()):
             raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must be a contiguous float32 [{B}, {dreg}] tensor")
-    check(load().tagrec_catsoftmax_bwd_f32(ptr(Q), _row_ld(Q), ptr(qrow), ptr(T), _row_ld(T), N, D, ptr(target), ptr(Qreg), ptr(Treg),
-                                           ldreg, dreg, B, float(temperature), n_split, ptr(workspace), workspace.numel(), ptr(lse),
-                                           ptr(g), ptr(dT), 0 if dT is None else _row_ld(dT), ptr(dQ), ptr(dQreg), ptr(dTreg), stream_ptr()), what)
+    check(load().tagrec_catsoftmax_bwd_f32(Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B,
+                                           float(temperature), n_split, workspace, workspace.numel(), lse, g, dT,
+                                           0 if dT is None else _row_ld(dT), dQ, dQreg, dTreg, stream_ptr()), what)
     return dQ
 
 
@@ -453,8 +448,8 @@ def directau_fwd(Ub, Ib, Ureg, Ireg, t, gamma):
     ls, parts, res = small[0:2], small[2:5], small[5:7]
     partials = torch.empty(2 * ((B + AU_PREP_ROWS - 1) // AU_PREP_ROWS) + 2 * ((B + AU_TILE - 1) // AU_TILE), dtype=torch.float32,
                            device=dev)
-    check(load().tagrec_directau_fwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, float(t), float(gamma),
-                                         ptr(inv), ptr(ls), ptr(partials), ptr(parts), ptr(res), stream_ptr()), "directau_fwd")
+    check(load().tagrec_directau_fwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, float(t), float(gamma), inv, ls, partials,
+                                         parts, res, stream_ptr()), "directau_fwd")
     return res, parts, AuState(float(t), float(gamma), inv, ls, parts)
 
 
@@ -473,8 +468,8 @@ def directau_bwd(Ub, Ib, Ureg, Ireg, state, g, dUb, dIb, dUreg, dIreg, what="dir
     for nm, t in (("dUb", dUb), ("dIb", dIb), ("dUreg", dUreg), ("dIreg", dIreg)):
         if t is not None and t.shape[0] != B:
             raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {B} rows")
-    check(load().tagrec_directau_bwd_f32(ptr(Ub), ptr(Ib), ld, D, ptr(Ureg), ptr(Ireg), ldreg, dreg, B, state.t, state.gamma,
-                                         ptr(inv), ptr(ls), ptr(g), ptr(dUb), ptr(dIb), ptr(dUreg), ptr(dIreg), stream_ptr()), what)
+    check(load().tagrec_directau_bwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, state.t, state.gamma, inv, ls, g, dUb, dIb,
+                                         dUreg, dIreg, stream_ptr()), what)
 
 
 def fold_rows(dst, rows, src, plan=None, accumulate=True):
@@ -526,7 +521,7 @@ def row_list_plan(rows, n, workspace=None, width=256):
     elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != rows.device or not workspace.is_contiguous():
         raise _lib.TagrecError(f"row_list_plan: the workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
     lib = load()
-    check(lib.tagrec_rowlist_plan_i64(ptr(rows), T, n, width, ptr(workspace), workspace.numel(), stream_ptr()), "rowlist_plan")
+    check(lib.tagrec_rowlist_plan_i64(rows, T, n, width, workspace, workspace.numel(), stream_ptr()), "rowlist_plan")
     p = RowListPlan()
     p.rows, p.n, p.width, p.workspace = rows, n, width, workspace
     at = [lib.tagrec_rowlist_plan_result(T, width, k) for k in range(4)]
@@ -549,8 +544,8 @@ def scatter_rows_ordered(dst, plan, src, accumulate):
         if not t.is_cuda or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
             raise _lib.TagrecError(f"scatter_rows_ordered: {nm} must be a float32 GPU tensor with unit inner stride")
     D = src.shape[1]
-    check(load().tagrec_row_scatter_ordered_f32(ptr(plan.workspace), plan.workspace.numel(), T, plan.width, ptr(src),
-                                                src.stride(0) if T > 1 else D, ptr(dst), dst.stride(0) if dst.shape[0] > 1 else D,
+    check(load().tagrec_row_scatter_ordered_f32(plan.workspace, plan.workspace.numel(), T, plan.width, src,
+                                                src.stride(0) if T > 1 else D, dst, dst.stride(0) if dst.shape[0] > 1 else D,
                                                 dst.shape[0], D, int(bool(accumulate)), stream_ptr()), "row_scatter_ordered")
     return dst
 

@@ -120,7 +120,7 @@ def sum_n(tensors, out=None):
         if not first:
             part = [out] + part
         arr = (_lib.c_void_p * len(part))(*[t.data_ptr() for t in part])
-        _lib.check(lib.tagrec_sum_n_f32(_lib.ptr(out), arr, len(part), out.numel(), _lib.stream_ptr()), "sum_n")
+        _lib.check(lib.tagrec_sum_n_f32(out, arr, len(part), out.numel(), _lib.stream_ptr()), "sum_n")
         first = False
     return out
 
@@ -175,9 +175,8 @@ class _NbrAttention(torch.autograd.Function):
         k, D = idx.shape[1], Ej.shape[1]
         attn = torch.empty(n, k, dtype=torch.float32, device=P.device)
         out = torch.empty(n, D, dtype=torch.float32, device=P.device)
-        _lib.check(_timed("attn_fwd", _lib.load().tagrec_tgcn_attn_fwd_f32, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(WT),
-                          _lib.ptr(v), _lib.ptr(Ej), _lib.ptr(idx), _lib.ptr(widx), n, k, D, A, _lib.ptr(attn),
-                          _lib.ptr(out), _lib.stream_ptr()), "tgcn_attn_fwd")
+        _lib.check(_timed("attn_fwd", _lib.load().tagrec_tgcn_attn_fwd_f32, P, Q, WT, v, Ej, idx, widx, n, k, D, A, attn, out,
+                          _lib.stream_ptr()), "tgcn_attn_fwd")
         ctx.save_for_backward(P, Q, WT, v, Ej, idx, widx, attn)
         return out
 
@@ -209,10 +208,8 @@ class _NbrAttention(torch.autograd.Function):
                 if nc > 0:
                     sel = lambda x: x.index_select(0, active)
                     Pc, idxc, widxc, attnc, doc = sel(P), sel(idx), sel(widx), sel(attn), sel(d_out)
-                    _lib.check(_timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, _lib.ptr(Pc), _lib.ptr(Q), _lib.ptr(WT),
-                                      _lib.ptr(v), _lib.ptr(Ej), _lib.ptr(idxc), _lib.ptr(widxc), _lib.ptr(attnc), _lib.ptr(doc),
-                                      nc, k, D, A, n_wt, _lib.ptr(dPc), _lib.ptr(dQ), _lib.ptr(dEj), _lib.ptr(dh),
-                                      _lib.ptr(dWT), _lib.ptr(dv), _lib.ptr(ws), ws_n, _lib.stream_ptr()), "tgcn_attn_bwd")
+                    _lib.check(_timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, Pc, Q, WT, v, Ej, idxc, widxc, attnc, doc, nc, k,
+                                      D, A, n_wt, dPc, dQ, dEj, dh, dWT, dv, ws, ws_n, _lib.stream_ptr()), "tgcn_attn_bwd")
                     if pull:
                         dQ, dEj = _pull_compact(idxc, attnc, doc, dh, Ej.shape[0])
                 else:
@@ -226,10 +223,8 @@ class _NbrAttention(torch.autograd.Function):
         else:                            # pull form: write dh, finish with two SpMMs over the inverted table
             dQ = dEj = None
             dh = torch.empty(n * k, A, dtype=torch.float32, device=P.device)
-        _lib.check(_timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(WT), _lib.ptr(v),
-                          _lib.ptr(Ej), _lib.ptr(idx), _lib.ptr(widx), _lib.ptr(attn), _lib.ptr(d_out),
-                          n, k, D, A, n_wt, _lib.ptr(dP), _lib.ptr(dQ), _lib.ptr(dEj), _lib.ptr(dh), _lib.ptr(dWT),
-                          _lib.ptr(dv), _lib.ptr(ws), ws_n, _lib.stream_ptr()), "tgcn_attn_bwd")
+        _lib.check(_timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, P, Q, WT, v, Ej, idx, widx, attn, d_out, n, k, D, A, n_wt, dP,
+                          dQ, dEj, dh, dWT, dv, ws, ws_n, _lib.stream_ptr()), "tgcn_attn_bwd")
         if inv is not None:
             torch.index_select(attn.reshape(-1), 0, inv.perm, out=inv.G.val)
             dEj = inv.G.spmm(d_out)
@@ -303,9 +298,8 @@ class _FusedDense(torch.autograd.Function):
         out = torch.empty(n, Dout, dtype=torch.float32, device=t0.device)
         bw = torch.empty(n, 3, dtype=torch.float32, device=t0.device)
         args = [x.contiguous() for x in (U, q, p, wb, w1, w2, w3, Wf, bf)]
-        _lib.check(_timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_f32, _lib.ptr(t0), _lib.ptr(t1), _lib.ptr(t2), n, D,
-                          Dout, U.shape[1], wb.shape[0], w1.shape[0], *[_lib.ptr(a) for a in args], _lib.ptr(bw),
-                          _lib.ptr(out), _lib.stream_ptr()), "tgcn_fuse_fwd")
+        _lib.check(_timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_f32, t0, t1, t2, n, D, Dout, U.shape[1], wb.shape[0],
+                          w1.shape[0], *args, bw, out, _lib.stream_ptr()), "tgcn_fuse_fwd")
         ctx.save_for_backward(t0, t1, t2, U, q, p, wb, w1, w2, w3, Wf, bf, out, bw)
         ctx.chunk_rows = chunk_rows
         return out
@@ -347,11 +341,9 @@ class _FusedDense(torch.autograd.Function):
         small = torch.empty(3 * C + 2 * A, dtype=torch.float32, device=dev)
         ws_n = lib.tagrec_tgcn_fuse_bwd_workspace(Dout)
         ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-        _lib.check(_timed("fuse_bwd", lib.tagrec_tgcn_fuse_bwd_f32, _lib.ptr(t0), _lib.ptr(t1), _lib.ptr(t2), n, D, Dout, A, C,
-                          V, _lib.ptr(U), _lib.ptr(q), _lib.ptr(p), _lib.ptr(wb), _lib.ptr(w1), _lib.ptr(w2), _lib.ptr(w3),
-                          _lib.ptr(Wf), _lib.ptr(out), _lib.ptr(d_out), _lib.ptr(dts[0]), _lib.ptr(dts[1]), _lib.ptr(dts[2]),
-                          _lib.ptr(yvec), _lib.ptr(dfeat), _lib.ptr(dS), _lib.ptr(small), _lib.ptr(ws), ws_n,
-                          _lib.stream_ptr()), "tgcn_fuse_bwd")
+        _lib.check(_timed("fuse_bwd", lib.tagrec_tgcn_fuse_bwd_f32, t0, t1, t2, n, D, Dout, A, C, V, U, q, p, wb, w1, w2, w3, Wf,
+                          out, d_out, dts[0], dts[1], dts[2], yvec, dfeat, dS, small, ws, ws_n, _lib.stream_ptr()),
+                   "tgcn_fuse_bwd")
         dwb, dq, dp = small[:3 * C].reshape(C, 3), small[3 * C:3 * C + A], small[3 * C + A:3 * C + 2 * A]
         # every gradient that is a product over the node axis: dWf, G (-> dw1, dw2, dw3) and dU, one launch
         from . import proj as PJ
@@ -360,9 +352,8 @@ class _FusedDense(torch.autograd.Function):
         res = torch.empty(res_n, dtype=torch.float32, device=dev)
         wf_n = lib.tagrec_tgcn_fuse_wf_workspace(D, Dout)
         wf_ws = torch.empty(wf_n, dtype=torch.float32, device=dev)
-        _lib.check(_timed("fuse_wf", lib.tagrec_tgcn_fuse_wf_f32, _lib.ptr(t0), _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(bw),
-                          _lib.ptr(yvec), _lib.ptr(wb), _lib.ptr(out), _lib.ptr(d_out), _lib.ptr(dfeat), _lib.ptr(dS), n, D,
-                          Dout, C, V, _lib.ptr(res), _lib.ptr(wf_ws), wf_n, _lib.stream_ptr()), "tgcn_fuse_wf")
+        _lib.check(_timed("fuse_wf", lib.tagrec_tgcn_fuse_wf_f32, t0, t1, t2, bw, yvec, wb, out, d_out, dfeat, dS, n, D, Dout, C,
+                          V, res, wf_ws, wf_n, _lib.stream_ptr()), "tgcn_fuse_wf")
         k_wf = Wf.numel()
         dWf = res[:k_wf].reshape(Wf.shape)
         G = res[k_wf:k_wf + 6 * V * 3 * D].reshape(6 * V, 3, D)            # G[f][j][d] = sum_nodes dfeat[f] e_j[d]

@@ -74,8 +74,7 @@ def attn_fwd(P, Q, WT, v, Ej, idx, widx, out=None):
     attn = torch.empty(n, k, dtype=torch.float32, device=P.device)
     if out is None:
         out = torch.empty(n, D, dtype=torch.float32, device=P.device)
-    _lib.check(TG._timed("attn_fwd", _lib.load().tagrec_tgcn_attn_fwd_f32, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(WT), _lib.ptr(v),
-                         _lib.ptr(Ej), _lib.ptr(idx), _lib.ptr(widx), n, k, D, A, _lib.ptr(attn), _lib.ptr(out),
+    _lib.check(TG._timed("attn_fwd", _lib.load().tagrec_tgcn_attn_fwd_f32, P, Q, WT, v, Ej, idx, widx, n, k, D, A, attn, out,
                          _lib.stream_ptr()), "tgcn_attn_fwd")
     return out, attn
 
@@ -90,10 +89,8 @@ def attn_bwd(P, Q, WT, v, Ej, idx, widx, attn, d_out, dQ, dEj, dh):
     dWT, dv = torch.empty_like(WT), torch.empty_like(v)
     ws_n = lib.tagrec_tgcn_attn_workspace(n_wt, A)
     ws = torch.empty(ws_n, dtype=torch.float32, device=P.device)
-    _lib.check(TG._timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(WT), _lib.ptr(v),
-                         _lib.ptr(Ej), _lib.ptr(idx), _lib.ptr(widx), _lib.ptr(attn), _lib.ptr(d_out), n, k, D, A, n_wt,
-                         _lib.ptr(dP), _lib.ptr(dQ), _lib.ptr(dEj), _lib.ptr(dh), _lib.ptr(dWT), _lib.ptr(dv), _lib.ptr(ws), ws_n,
-                         _lib.stream_ptr()), "tgcn_attn_bwd")
+    _lib.check(TG._timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_f32, P, Q, WT, v, Ej, idx, widx, attn, d_out, n, k, D, A, n_wt, dP,
+                         dQ, dEj, dh, dWT, dv, ws, ws_n, _lib.stream_ptr()), "tgcn_attn_bwd")
     return dP, dWT, dv
 
 
@@ -122,38 +119,35 @@ def attn_bwd_pulls(P, Q, WT, v, Ej, idx, widx, attn, d_out, addQ, addX, w_major=
         skey = torch.empty(n * k, dtype=torch.int32, device=dev)
         fw_n = lib.tagrec_inv_filter_workspace(perm32.numel())
         fw = torch.empty(fw_n, dtype=torch.int32, device=dev)
-        _lib.check(TG._timed("attn_invert", lib.tagrec_inv_filter_i32, _lib.ptr(perm32), _lib.ptr(dest32), perm32.numel(), k,
-                             _lib.ptr(pos_src), _lib.ptr(pos_dst), _lib.ptr(attn), n_dst, n * k, _lib.ptr(skey), _lib.ptr(pair),
-                             _lib.ptr(src), _lib.ptr(val), _lib.ptr(fw), fw_n, _lib.stream_ptr()), "inv_filter")
+        _lib.check(TG._timed("attn_invert", lib.tagrec_inv_filter_i32, perm32, dest32, perm32.numel(), k, pos_src, pos_dst, attn,
+                             n_dst, n * k, skey, pair, src, val, fw, fw_n, _lib.stream_ptr()), "inv_filter")
     else:
         key = torch.empty(n * k, dtype=torch.int32, device=dev)
-        _lib.check(lib.tagrec_attn_keys_i32(_lib.ptr(idx), n * k, n_dst, _lib.ptr(key), _lib.stream_ptr()), "attn_keys")
+        _lib.check(lib.tagrec_attn_keys_i32(idx, n * k, n_dst, key, _lib.stream_ptr()), "attn_keys")
         skey, order = torch.sort(key, stable=True)
-        _lib.check(lib.tagrec_attn_invert_fill(_lib.ptr(order), _lib.ptr(attn), k, n * k, _lib.ptr(pair), _lib.ptr(src), _lib.ptr(val),
-                                               _lib.stream_ptr()), "attn_invert_fill")
+        _lib.check(lib.tagrec_attn_invert_fill(order, attn, k, n * k, pair, src, val, _lib.stream_ptr()), "attn_invert_fill")
     rowptr = torch.searchsorted(skey, torch.arange(n_dst + 1, dtype=torch.int32, device=dev))
     inv = Graph(rowptr, src, val, (n_dst, n), workspace=True, deferred=True)
     da = torch.empty(n * k, dtype=torch.float32, device=dev)
     dEj = out if out is not None else torch.empty(n_dst, D, dtype=torch.float32, device=dev)      # (may alias addX: element-wise)
-    _lib.check(TG._timed("attn_pull_da", lib.tagrec_attn_pull_da_f32, inv.handle, _lib.ptr(pair), _lib.ptr(d_out), _lib.ptr(Ej),
-                         _lib.ptr(addX), _lib.ptr(dEj), _lib.ptr(da), D, _lib.stream_ptr()), "attn_pull_da")
+    _lib.check(TG._timed("attn_pull_da", lib.tagrec_attn_pull_da_f32, inv.handle, pair, d_out, Ej, addX, dEj, da, D,
+                         _lib.stream_ptr()), "attn_pull_da")
     dP = torch.empty_like(P)
     dWT, dv = torch.empty_like(WT), torch.empty_like(v)
     comp = torch.empty(n * k, 2, dtype=torch.float32, device=dev)
     ws_n = lib.tagrec_tgcn_attn_workspace(n_wt, A)
     ws = torch.empty(ws_n, dtype=torch.float32, device=dev)
-    _lib.check(TG._timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_ds_f32, _lib.ptr(P), _lib.ptr(Q), _lib.ptr(WT), _lib.ptr(v), _lib.ptr(idx),
-                         _lib.ptr(widx), _lib.ptr(attn), _lib.ptr(da), n, k, A, n_wt, int(w_major), _lib.ptr(dP), _lib.ptr(comp), _lib.ptr(dWT),
-                         _lib.ptr(dv), _lib.ptr(ws), ws_n, _lib.stream_ptr()), "tgcn_attn_bwd_ds")
+    _lib.check(TG._timed("attn_bwd", lib.tagrec_tgcn_attn_bwd_ds_f32, P, Q, WT, v, idx, widx, attn, da, n, k, A, n_wt,
+                         int(w_major), dP, comp, dWT, dv, ws, ws_n, _lib.stream_ptr()), "tgcn_attn_bwd_ds")
     if SEGMENTED_DQ:         # balanced segmented sum over the sorted pair list, float atomics at segment ends (adds into addQ)
         dQ = addQ if addQ is not None else torch.zeros(n_dst, A, dtype=torch.float32, device=dev)
-        _lib.check(TG._timed("attn_pull_dq", lib.tagrec_attn_seg_dq_f32, _lib.ptr(skey), _lib.ptr(pair), n * k, n_dst, _lib.ptr(comp),
-                             _lib.ptr(v), A, _lib.ptr(dQ), _lib.stream_ptr()), "attn_seg_dq")
+        _lib.check(TG._timed("attn_pull_dq", lib.tagrec_attn_seg_dq_f32, skey, pair, n * k, n_dst, comp, v, A, dQ,
+                             _lib.stream_ptr()), "attn_seg_dq")
     else:                    # row-per-wave pull on the inverted table (deterministic order)
         dQ = torch.empty(n_dst, A, dtype=torch.float32, device=dev)
         inv = inv.like(pair, val, n * k)                    # the same rows, colidx = pair ids
-        _lib.check(TG._timed("attn_pull_dq", lib.tagrec_attn_pull_dq_f32, inv.handle, _lib.ptr(comp), _lib.ptr(v), A, _lib.ptr(addQ),
-                             _lib.ptr(dQ), _lib.stream_ptr()), "attn_pull_dq")
+        _lib.check(TG._timed("attn_pull_dq", lib.tagrec_attn_pull_dq_f32, inv.handle, comp, v, A, addQ, dQ, _lib.stream_ptr()),
+                   "attn_pull_dq")
     return dP, dWT, dv, dQ, dEj
 
 
@@ -168,14 +162,12 @@ def fuse_fwd(t0, t1, t2, dp, drop=None):
     if drop is not None:
         pk, seeds, rows, lo1, lo2 = drop
         seeds3 = (_lib.ctypes.c_uint64 * 3)(*[int(x) for x in seeds])
-        _lib.check(TG._timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_drop_f32, _lib.ptr(t0), _lib.ptr(t1), _lib.ptr(t2), n, D,
-                             Wf.shape[1], U.shape[1], wb.shape[0], w1.shape[0], *[_lib.ptr(a) for a in dp], float(pk), seeds3,
-                             _lib.ptr(rows[0]), _lib.ptr(rows[1]), _lib.ptr(rows[2]), int(lo1), int(lo2), _lib.ptr(bw),
-                             _lib.ptr(out), _lib.stream_ptr()), "tgcn_fuse_fwd_drop")
+        _lib.check(TG._timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_drop_f32, t0, t1, t2, n, D, Wf.shape[1], U.shape[1],
+                             wb.shape[0], w1.shape[0], *dp, float(pk), seeds3, rows[0], rows[1], rows[2], int(lo1), int(lo2), bw,
+                             out, _lib.stream_ptr()), "tgcn_fuse_fwd_drop")
         return out, bw
-    _lib.check(TG._timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_f32, _lib.ptr(t0), _lib.ptr(t1), _lib.ptr(t2), n, D,
-                         Wf.shape[1], U.shape[1], wb.shape[0], w1.shape[0], *[_lib.ptr(a) for a in dp], _lib.ptr(bw),
-                         _lib.ptr(out), _lib.stream_ptr()), "tgcn_fuse_fwd")
+    _lib.check(TG._timed("fuse_fwd", _lib.load().tagrec_tgcn_fuse_fwd_f32, t0, t1, t2, n, D, Wf.shape[1], U.shape[1], wb.shape[0],
+                         w1.shape[0], *dp, bw, out, _lib.stream_ptr()), "tgcn_fuse_fwd")
     return out, bw
 
 
@@ -282,9 +274,9 @@ def step_forward(model, batch, embs, ew, layers_ps, training_drop):
                 kk = model.nbr[r][0].shape[1]
                 idx = torch.empty(m[src], kk, dtype=torch.int32, device=dev)
                 widx = torch.empty(m[src], kk, dtype=torch.int32, device=dev)
-                _lib.check(lib.tagrec_nbr_gather_i32(_lib.ptr(model.nbr[r][0]), _lib.ptr(model.nbr[r][1]), _lib.ptr(rows),
-                                                     _lib.ptr(pos_in[nb] if rows_in[nb] is not None else None), m[src], kk,
-                                                     _lib.ptr(idx), _lib.ptr(widx), _lib.stream_ptr()), "nbr_gather")
+                _lib.check(lib.tagrec_nbr_gather_i32(model.nbr[r][0], model.nbr[r][1], rows,
+                                                     pos_in[nb] if rows_in[nb] is not None else None, m[src], kk, idx, widx,
+                                                     _lib.stream_ptr()), "nbr_gather")
             _, attns[r] = attn_fwd(P[(src, nb)], Q[nb], WT[nb], att[nb][3].reshape(-1), X[nb], idx, widx,
                                    out=T3[SLOT[nb]][rng[src]])
             idxs[r] = (idx, widx)

@@ -122,22 +122,19 @@ class Adam:
                 small.setdefault(st["t"], []).append((p.data, g, st["m"], st["v"]))       # one launch for all of them, below
                 continue
             if self.capturable:
-                _lib.check(lib.tagrec_adam_graph_f32(_lib.ptr(p.data), _lib.ptr(g), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                                     p.numel(), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                     _lib.ptr(st["t_dev"]), _lib.ptr(st["coef"]), _lib.stream_ptr()),
-                           "adam_graph")
+                _lib.check(lib.tagrec_adam_graph_f32(p.data, g, st["m"], st["v"], p.numel(), self.lr, self.betas[0], self.betas[1],
+                                                     self.eps, st["t_dev"], st["coef"], _lib.stream_ptr()), "adam_graph")
             else:
-                _lib.check(lib.tagrec_adam_f32(_lib.ptr(p.data), _lib.ptr(g), _lib.ptr(st["m"]), _lib.ptr(st["v"]),
-                                               p.numel(), self.lr, self.betas[0], self.betas[1], self.eps, st["t"],
-                                               _lib.stream_ptr()), "adam")
+                _lib.check(lib.tagrec_adam_f32(p.data, g, st["m"], st["v"], p.numel(), self.lr, self.betas[0], self.betas[1],
+                                               self.eps, st["t"], _lib.stream_ptr()), "adam")
         # the small tensors (a TGCN layer has 21): launches of up to 64 tensors each instead of a burst of tiny launches, during
         # which the GPU caught up with the host at the end of every step
         for t, group in small.items():
             k = len(group)
             if k < 3:                                     # a model with one or two tensors: the plain launch is cheaper to set up
                 for pd, g_, m_, v_ in group:
-                    _lib.check(lib.tagrec_adam_f32(_lib.ptr(pd), _lib.ptr(g_), _lib.ptr(m_), _lib.ptr(v_), pd.numel(), self.lr,
-                                                   self.betas[0], self.betas[1], self.eps, t, _lib.stream_ptr()), "adam")
+                    _lib.check(lib.tagrec_adam_f32(pd, g_, m_, v_, pd.numel(), self.lr, self.betas[0], self.betas[1], self.eps, t,
+                                                   _lib.stream_ptr()), "adam")
                 continue
             arr = [(_lib.ctypes.c_void_p * k)(*[x[i].data_ptr() for x in group]) for i in range(4)]
             n = (_lib.ctypes.c_int64 * k)(*[x[0].numel() for x in group])

@@ -99,9 +99,8 @@ class _Positives:
             return (neg, neg.new_empty((0, n_cand)), None if n_cand == 1 else neg.new_empty((0, n_cand), dtype=torch.float32)) \
                 if return_candidates else neg
         if n_cand == 1 and alias is None and not return_candidates:
-            _lib.check(_lib.load().tagrec_sample_negative_i64(_lib.ptr(left), left.numel(), _lib.ptr(self.rowptr),
-                                                              _lib.ptr(self.cols), self.n_left, self.n_right, int(seed),
-                                                              _lib.ptr(neg), _lib.stream_ptr()), "sample_negative")
+            _lib.check(_lib.load().tagrec_sample_negative_i64(left, left.numel(), self.rowptr, self.cols, self.n_left,
+                                                              self.n_right, int(seed), neg, _lib.stream_ptr()), "sample_negative")
             return neg
         prob = idx = None
         if alias is not None:
@@ -121,9 +120,8 @@ class _Positives:
         score = torch.empty((left.numel(), n_cand), dtype=torch.float32, device=left.device) \
             if return_candidates and n_cand != 1 else None
         _lib.check(_lib.load().tagrec_sample_negative_ex_i64(
-            _lib.ptr(left), left.numel(), _lib.ptr(self.rowptr), _lib.ptr(self.cols), self.n_left, self.n_right, int(seed),
-            int(n_cand), _lib.ptr(prob), _lib.ptr(idx), _lib.ptr(U), ld_u, _lib.ptr(I), ld_i, D, _lib.ptr(neg), _lib.ptr(cand),
-            _lib.ptr(score), _lib.stream_ptr()), "sample_negative_ex")
+            left, left.numel(), self.rowptr, self.cols, self.n_left, self.n_right, int(seed), int(n_cand), prob, idx, U, ld_u, I, ld_i,
+            D, neg, cand, score, _lib.stream_ptr()), "sample_negative_ex")
         return (neg, cand, score) if return_candidates else neg
 
     @staticmethod

@@ -459,6 +459,30 @@ int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, 
                               int64_t B, float temperature, int n_split, void* workspace, int64_t workspace_bytes,
                               const float* lse, const float* g, float* dT, int64_t lddt, float* dQ, float* dQreg, float* dTreg,
                               void* stream);
+/* The MASKED form: the two calls above with a list of excluded columns per row of Q, a CSR in the conventions of
+ * tagrec_eval_topk_f32's train lists: mask_ptr int64 [rows of Q + 1], mask_cols int32, ascending and unique within a row;
+ * batch row b uses CSR row qrow[b] (qrow NULL: row b).  With E_b = list(qrow_b) \ {target_b}
+ *   loss_b = log sum_{n not in E_b} exp(z_bn) - z_{b, target_b},   C_bn = 0 EXACTLY for n in E_b
+ * (an excluded column is never added to a row's running sum and its coefficient is a stored 0.0f, not a product); the target
+ * column stays live whether or not the list names it.  A row whose only live column is its target has lse_b == zt_b bit
+ * for bit, and the backward, which finds such a row by the length of its list, takes p_target = 1: the row's coefficients,
+ * its dQ row and its share of dT are exactly 0 (formed from the logits they would be the rounding residue of zt).  Everything
+ * else -- the split, the workspace (same size), the L2 part, the orders of summation, now a function of (B, N, D, n_split,
+ * lists) -- is as above, and with every list empty the outputs are the unmasked calls' bits (N = 1 aside: there every
+ * row is such a row).  N <= 2^31 - 1
+ * (TAGREC_E_UNSUPPORTED otherwise); both pointers are required.  The lists are not validated: an unsorted list gives an
+ * unspecified mask, but no read leaves [mask_ptr[r], mask_ptr[r + 1]) of mask_cols. */
+int tagrec_catsoftmax_masked_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                     int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                     int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                     int64_t workspace_bytes, float* lse, float* zt, float* loss_out, void* stream,
+                                     const int64_t* mask_ptr, const int32_t* mask_cols);
+int tagrec_catsoftmax_masked_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                     int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                     int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                     int64_t workspace_bytes, const float* lse, const float* g, float* dT, int64_t lddt,
+                                     float* dQ, float* dQreg, float* dTreg, void* stream, const int64_t* mask_ptr,
+                                     const int32_t* mask_cols);
 
 /* ---- DirectAU on COMPACT rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
  * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub; repeated rows are kept.

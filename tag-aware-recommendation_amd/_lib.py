@@ -49,6 +49,10 @@ def refuse_multi_negative(config, what):
     if over != "negatives":
         raise TagrecError(f"{what}: softmax_over={over!r} is not covered (the softmax over the catalogue: the LightGCN and NGCF "
                           "steps and BPR_training_data only); it takes softmax_over=\"negatives\"")
+    mask = config.get("catalogue_mask", "none")
+    if mask != "none":
+        raise TagrecError(f"{what}: catalogue_mask={mask!r} is not covered (it masks the softmax over the catalogue of the "
+                          "LightGCN and NGCF steps); it takes catalogue_mask=\"none\"")
     neg = config.get("negatives", "sampled")
     if neg != "sampled":
         raise TagrecError(f"{what}: negatives={neg!r} is not covered (in-batch negatives: the LightGCN and NGCF steps and "

@@ -32,6 +32,8 @@ _BASE = {
     "in_batch_logq": False,       # in-batch: subtract log(train degree of the item / train edges) from every column's logit
     # what the "softmax" loss normalises over (LightGCN, NGCF and BPR_training_data)
     "softmax_over": "negatives",  # "catalogue": every item (rowops.catsoftmax_*); batches are [B, 2], nothing is sampled
+    # softmax_over="catalogue" only: which columns leave a row's softmax (LightGCN, NGCF; SimGCL's ranking part)
+    "catalogue_mask": "none",     # "train_positives": the user's OTHER train items (help.user_positives_csr), as at evaluation
     # BPR_training_data: produce [E, 2] = (user, positive) epoch arrays without launching the sampler (the in-batch branch)
     # for objectives that take no negatives (DirectAU); the other producers do not read it
     "pair_batches": False,
@@ -41,6 +43,7 @@ MAX_NEG_CANDIDATES = 16
 MUL_LOSS_FUNCS = ("softplus", "logsigmoid", "softmax")
 NEGATIVES_MODES = ("sampled", "in_batch")
 SOFTMAX_OVER = ("negatives", "catalogue")
+CATALOGUE_MASKS = ("none", "train_positives")
 MAX_NEGATIVES = 63                # the kernel keeps the K + 1 scores of a tuple one per lane of a 64-lane wavefront
 
 # utility/config.py:1-12, 41-52
@@ -81,6 +84,7 @@ def get_config(model="lightgcn", **overrides):
     check_ranking(cfg)
     check_negatives(cfg)
     check_softmax_over(cfg)
+    check_catalogue_mask(cfg)
     if model == "simgcl":
         check_contrastive(cfg)
     if model == "directau":
@@ -151,6 +155,19 @@ def check_softmax_over(cfg):
         if neg != "sampled":
             raise TagrecError(f"softmax_over=\"catalogue\" is not mixed with negatives={neg!r}: it needs negatives=\"sampled\"")
     return over == "catalogue"
+
+
+def check_catalogue_mask(cfg):
+    """The catalogue_mask key of a config -> whether a user's other train positives leave the catalogue softmax; an unknown
+    value, and "train_positives" without softmax_over="catalogue" (there is no catalogue to mask), is refused."""
+    from ._lib import TagrecError
+    mask = cfg.get("catalogue_mask", "none")
+    if mask not in CATALOGUE_MASKS:
+        raise TagrecError(f"unknown catalogue_mask {mask!r} (have {CATALOGUE_MASKS})")
+    if mask != "none" and cfg.get("softmax_over", "negatives") != "catalogue":
+        raise TagrecError(f"catalogue_mask={mask!r} masks columns of the softmax over the catalogue: it needs "
+                          f"softmax_over=\"catalogue\", got {cfg.get('softmax_over', 'negatives')!r}")
+    return mask == "train_positives"
 
 
 def check_contrastive(cfg):

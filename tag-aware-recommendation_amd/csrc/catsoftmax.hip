@@ -14,6 +14,17 @@
 //     dT: no atomics anywhere, nothing reads the old contents, every order is a function of (B, N, D, n_split) only.
 // The target logit zt[b] comes from the same MFMA tile that feeds the row sum (stored by the lane that meets column
 // target_b), so lse_b >= zt_b holds in floating point: the maximum is exact, the term of the maximum is exactly 1.
+//
+// The MASKED form (tagrec_catsoftmax_masked_*): row b leaves the columns of a sorted list out of its softmax, all but its own
+// target -- mask_ptr / mask_cols, a CSR over the rows of Q in csrc/eval.hip's conventions, row qrow[b].  It is a compile-time
+// variant of the same body (the unmasked instantiations are the code they were): an excluded column is a select in the tile
+// walk, never pushed onto the running pair in the forward and an exact 0.0f coefficient in both backward walks.
+//   * owner = rows of Q (forward, dQ): a lane meets its columns in ascending order, so it keeps one cursor into its row's list
+//     and the next excluded id in a register; a tile below that id costs one compare and no load.
+//   * owner = rows of T (dT): the 64 threads that stage the walked rows' targets fold each row's entries inside the owned 64
+//     columns into one 64-bit word, a ballot per column transposes the 64 words and they go to LDS (two buffers of 64
+//     words): a lane of the walk reads the one word of its column.  The search for the NEXT walked tile is issued before the
+//     current tile's MFMAs and written to the other buffer.
 #include "pairtile.h"
 
 namespace tagrec {
@@ -37,17 +48,90 @@ struct CatArgs {
   float* dQpart;                          // [n_split, B, D] partial rows (dQ itself when n_split == 1)
   float* dT;
   int64_t lddt;
+  const int64_t* mask_ptr;                // the masked form: CSR over the rows of Q (row qrow[b]) of the excluded columns,
+  const int32_t* mask_cols;               // ascending and unique within a row; the row's own target stays live regardless
 };
 
+constexpr int64_t kNoCol = INT64_MAX;     // "no further excluded column" of a lane's cursor
+
+// One row of the CSR as 32-bit state (a column id fits int32; a list longer than 2^31 - 1 entries is cut there).
+struct MaskRow {
+  const int32_t* cols;
+  int n;
+};
+__device__ __forceinline__ MaskRow mask_row(const CatArgs& a, int64_t r) {
+  const int64_t lo = a.mask_ptr[r], len = a.mask_ptr[r + 1] - lo;
+  return {a.mask_cols + lo, len < 0 ? 0 : (len > INT32_MAX ? INT32_MAX : static_cast<int>(len))};
+}
+
+// first position in [0, n) whose column is >= col (n if none); every read lies inside the row whatever the list holds
+__device__ __forceinline__ int mask_lower_bound(const MaskRow& m, int col) {
+  int lo = 0, hi = m.n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (m.cols[mid] < col) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Is the row's target its ONLY live column (the list holds every other column)?  Then p_target = 1 and every coefficient of
+// the row is 0; the backward walks take the target for excluded as well, so that the 0 is a stored one.  (Formed from the
+// logits it would be expf(z - lse) - 1 with lse == zt bit for bit, where z - lse, contracted into one fma, sees the
+// unrounded product and leaves the rounding residue of zt.)  The usual row fails the first compare.
+__device__ __forceinline__ bool mask_single(const MaskRow& m, int64_t N, int64_t tgt) {
+  if (m.n < N - 1) return false;
+  const int c = mask_lower_bound(m, static_cast<int>(tgt));
+  const bool has = c < m.n && m.cols[c] == tgt;
+  return m.n - (has ? 1 : 0) == N - 1;
+}
+
+// MODE 2 of the masked form: bit d of the word = "column own0 + d is excluded for the walked row w" (the row's target never is)
+__device__ __forceinline__ uint64_t mask_word(const CatArgs& a, int64_t w, int64_t own0) {
+  if (w >= a.B) return 0;
+  const MaskRow m = mask_row(a, a.q.idx ? a.q.idx[w] : w);
+  const int first = static_cast<int>(own0);            // own0 < N <= 2^31 - 1
+  uint64_t bits = 0;
+  for (int c = mask_lower_bound(m, first); c < m.n; ++c) {
+    const unsigned d = static_cast<unsigned>(m.cols[c]) - static_cast<unsigned>(first);
+    if (d >= static_cast<unsigned>(kTile)) break;      // past the owned columns (or, in an unsorted list, before them)
+    bits |= 1ull << d;
+  }
+  const int64_t tgt = a.target[w], dt = tgt - own0;
+  if (dt >= 0 && dt < kTile) {
+    bits &= ~(1ull << dt);
+    if (mask_single(m, a.N, tgt)) bits |= 1ull << dt;
+  }
+  return bits;
+}
+
+// The first wavefront of a block (lane = walked row w0 + lane) turns its 64 row words into 64 COLUMN words -- bit i of dst[d] =
+// "owned column own0 + d is excluded for walked row w0 + i" -- by one ballot per column, so that a lane of the tile walk reads
+// the one word of its own column.  No entry in the whole 64 x 64 tile (the usual case at catalogue scale): one ballot.
+__device__ __forceinline__ void stage_mask_words(uint64_t* dst, const CatArgs& a, int64_t w0, int64_t own0, int lane) {
+  const uint64_t bits = mask_word(a, w0 + lane, own0);
+  uint64_t mine = 0;
+  if (__ballot(bits != 0) != 0) {
+#pragma unroll 1
+    for (int d = 0; d < kTile; ++d) {
+      const uint64_t col = __ballot(static_cast<int>((bits >> d) & 1ull));
+      if (lane == d) mine = col;
+    }
+  }
+  dst[lane] = mine;
+}
+
 // MODE 0: forward (owner = 64 rows of Q, walks one column range).  MODE 1: backward of Q, the same roles.
-// MODE 2: backward of T (owner = 64 rows of T, walks all B rows of Q).
-template <int MODE, int NF>
+// MODE 2: backward of T (owner = 64 rows of T, walks all B rows of Q).  MASKED: the lists of a.mask_ptr / a.mask_cols apply.
+template <int MODE, int NF, bool MASKED>
 __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) {
   constexpr int S = tile_stride(16 * NF);
   int64_t* sh_tgt = reinterpret_cast<int64_t*>(smem);  // MODE 2: targets and row log-sum-exps of the walked rows
   float* sh_lse = reinterpret_cast<float*>(sh_tgt + kTile);
   float* sh_own = sh_lse + kTile;
   float* sh_walk = sh_own + kTile * S;
+  // MASKED, MODE 2: one 64-bit word per owned column (stage_mask_words), twice: the words of the next walked tile are written
+  // while this one's are read
+  uint64_t* sh_bits = reinterpret_cast<uint64_t*>(sh_walk + kTile * S);
 
   const PairLane ln = pair_lane();
   const int tid = threadIdx.x, wave = ln.wave, r = ln.r, q = ln.q;
@@ -78,6 +162,24 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
   AccTiles<NF> acc;
   zero_acc(acc);
 
+  // MASKED, MODE 0 / 1: the lane's cursor into the list of its row and the column it stands on (kNoCol: the list is spent)
+  MaskRow m_row = {nullptr, 0};
+  int m_cur = 0;
+  int64_t m_next = kNoCol;
+  bool m_single = false;                               // MODE 1: `mask_single` of the lane's row
+  int m_buf = 0;                                       // MASKED, MODE 2: the half of sh_bits this tile reads
+  if constexpr (MASKED && MODE != 2) {
+    if (o_ok && w_begin < w_end) {
+      m_row = mask_row(a, own.idx ? own.idx[o] : o);
+      m_cur = mask_lower_bound(m_row, static_cast<int>(w_begin));                // a range starts mid-list
+      if (m_cur < m_row.n) m_next = m_row.cols[m_cur];
+      if (MODE == 1) m_single = mask_single(m_row, a.N, o_tgt);
+    }
+  }
+  if constexpr (MASKED && MODE == 2) {
+    if (tid < kTile) stage_mask_words(sh_bits, a, w_begin, own0, tid);         // the first barrier of the walk covers it
+  }
+
   if (w_begin < w_end) load_tile<NF>(pre, walk, a.D, w_begin, w_end);
   for (int64_t w0 = w_begin; w0 < w_end; w0 += kTile) {
     __syncthreads();                                   // the previous walked tile has been consumed
@@ -90,9 +192,26 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
     }
     __syncthreads();
     if (w0 + kTile < w_end) load_tile<NF>(pre, walk, a.D, w0 + kTile, w_end);   // in flight under this tile's MFMAs
+    if constexpr (MASKED && MODE == 2) {               // and so is the search of the next walked rows' lists
+      if (tid < kTile && w0 + kTile < w_end) stage_mask_words(sh_bits + kTile * (m_buf ^ 1), a, w0 + kTile, own0, tid);
+    }
+
+    // MASKED, MODE 0 / 1: bit 4 t + v = "column w0 + 16 t + 4 q + v is in the row's list".  The usual tile holds no entry:
+    // one compare.  Otherwise every entry of the tile is passed once, whichever of the row's four lanes it belongs to.
+    unsigned m_ex = 0;
+    if constexpr (MASKED && MODE != 2) {
+      while (m_next < w0 + kTile) {
+        const int d = static_cast<int>(m_next - w0);
+        if (d >= 0 && ((d >> 2) & 3) == q) m_ex |= 1u << (((d >> 4) << 2) | (d & 3));
+        ++m_cur;
+        m_next = m_cur < m_row.n ? m_row.cols[m_cur] : kNoCol;
+      }
+    }
 
     f32x4 sc[4];
     score_tile(sh_own, sh_walk, S, a.Dk, ln, sc);
+    uint64_t m_col = 0;                                // MASKED, MODE 2: the word of this lane's column, walked row 4 q at bit 0
+    if constexpr (MASKED && MODE == 2) m_col = sh_bits[kTile * m_buf + 16 * wave + r] >> (4 * q);
     // sc[t][v] = owned row o . walked row w0 + 16 t + 4 q + v
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -100,7 +219,9 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
       for (int v = 0; v < 4; ++v) {
         const int wl = 16 * t + 4 * q + v;
         const int64_t w = w0 + wl;
-        const bool live = o_ok && w < w_end;
+        bool live = o_ok && w < w_end;
+        if constexpr (MASKED && MODE != 2) live = live && (w == o_tgt ? !m_single : ((m_ex >> (4 * t + v)) & 1u) == 0);
+        if constexpr (MASKED && MODE == 2) live = live && ((m_col >> (16 * t + v)) & 1ull) == 0;
         const float z = sc[t][v] * a.inv_tau;          // one rounding, the same in every pass
         if (MODE == 0) {
           if (live) {
@@ -115,6 +236,7 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
       }
     }
     if (MODE != 0) grad_tile<NF>(sh_walk, S, ln, sc, acc);
+    if constexpr (MASKED && MODE == 2) m_buf ^= 1;
   }
 
   if (MODE == 0) {
@@ -142,19 +264,41 @@ __device__ __forceinline__ void cat_body(const CatArgs& a, unsigned char* smem) 
 template <int NF>
 __global__ __launch_bounds__(kThreads) void cat_fwd_kernel(CatArgs a) {
   extern __shared__ __align__(16) unsigned char cat_smem[];
-  cat_body<0, NF>(a, cat_smem);
+  cat_body<0, NF, false>(a, cat_smem);
 }
 
 template <int NF>
 __global__ __launch_bounds__(kThreads) void cat_dq_kernel(CatArgs a) {
   extern __shared__ __align__(16) unsigned char cat_smem[];
-  cat_body<1, NF>(a, cat_smem);
+  cat_body<1, NF, false>(a, cat_smem);
 }
 
 template <int NF>
 __global__ __launch_bounds__(kThreads) void cat_dt_kernel(CatArgs a) {
   extern __shared__ __align__(16) unsigned char cat_smem[];
-  cat_body<2, NF>(a, cat_smem);
+  cat_body<2, NF, false>(a, cat_smem);
+}
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) void cat_fwd_masked_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<0, NF, true>(a, cat_smem);
+}
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) void cat_dq_masked_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<1, NF, true>(a, cat_smem);
+}
+
+// Left to itself the register allocator stops a few registers above the unmasked kernel's step at NF = 4 and 8 (a wave of
+// occupancy each); asked for the unmasked kernel's waves per SIMD it fits every NF, still without scratch.
+constexpr int dt_waves(int nf) { return nf <= 1 ? 6 : nf == 2 ? 5 : nf == 4 ? 4 : nf == 8 ? 3 : nf == 12 ? 2 : 1; }
+
+template <int NF>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(dt_waves(NF)))) void cat_dt_masked_kernel(CatArgs a) {
+  extern __shared__ __align__(16) unsigned char cat_smem[];
+  cat_body<2, NF, true>(a, cat_smem);
 }
 
 struct RegArgs {
@@ -174,7 +318,8 @@ __device__ __forceinline__ const float* reg_row(const RegArgs& x, int side, int6
   return x.Treg + t * x.ldreg;
 }
 
-// lse[b] = merge of the row's (maximum, sum) pairs in ascending range order; partials[2 blk] = sum of (lse - zt) over the
+// lse[b] = merge of the row's (maximum, sum) pairs in ascending range order (a range that is empty, or in the masked form
+// wholly excluded for the row, holds (sentinel, 0) and merges as nothing: its side of lse_merge is 0 * expf(<= 0)); partials[2 blk] = sum of (lse - zt) over the
 // block's 256 rows (fixed tree), partials[2 blk + 1] = 0.5 sum |row|^2 of their L2 rows (one row per wavefront at a time)
 __global__ __launch_bounds__(kThreads) void cat_combine_kernel(const float* pm, const float* ps, int n_split, int64_t B,
                                                                const float* zt, RegArgs x, float* lse_out, float* partials) {
@@ -187,7 +332,7 @@ __global__ __launch_bounds__(kThreads) void cat_combine_kernel(const float* pm, 
   if (b < B) {
     float m = kLowest, s = 0.f;
     for (int y = 0; y < n_split; ++y) lse_merge(m, s, pm[static_cast<int64_t>(y) * B + b], ps[static_cast<int64_t>(y) * B + b]);
-    const float l = m + logf(s);                       // range 0 is never empty: m is a score, s >= 1
+    const float l = m + logf(s);                       // the target's range is live: m is a score, its term is 1, s >= 1
     lse_out[b] = l;
     loss = l - zt[b];
   }
@@ -231,8 +376,8 @@ __global__ __launch_bounds__(kThreads) void cat_reg_bwd_kernel(RegArgs x, int64_
   dTreg[i] = rscale * reg_row(x, 1, b)[c];
 }
 
-size_t lds_bytes(int Dp) {
-  return kTile * sizeof(int64_t) + kTile * sizeof(float) + tiles_bytes(Dp);
+size_t lds_bytes(int Dp, bool masked = false) {
+  return kTile * sizeof(int64_t) + kTile * sizeof(float) + tiles_bytes(Dp) + (masked ? 2 * kTile * sizeof(uint64_t) : 0);
 }
 
 bool shape_ok(int64_t B, int64_t N, int D) { return D >= 8 && D <= 256 && (D & 3) == 0 && B >= 1 && B <= 65536 && N >= 1; }
@@ -304,20 +449,30 @@ extern "C" int64_t tagrec_catsoftmax_workspace(int64_t B, int64_t N, int D, int 
   return 4 * workspace_floats(B, D, n_split == 0 ? default_splits(B, N) : n_split);
 }
 
-extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
-                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
-                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
-                                         int64_t workspace_bytes, float* lse, float* zt, float* loss_out, void* stream) {
-  if (int rc = check_shape("catsoftmax_fwd", B, N, D, ldq, ldt)) return rc;
-  TAGREC_REQUIRE(Q && T && target && workspace && lse && zt && loss_out, "catsoftmax_fwd: null pointer");
-  TAGREC_REQUIRE((Qreg == nullptr) == (Treg == nullptr), "catsoftmax_fwd: Qreg/Treg must both be given or both null");
-  TAGREC_REQUIRE(!Qreg || (Dreg >= 1 && ldreg >= Dreg), "catsoftmax_fwd: bad reg shape");
-  if (int rc = check_temperature("catsoftmax_fwd", temperature)) return rc;
+// the two entry-point pairs; masked: the lists are required and a column id must fit mask_cols' int32
+static int cat_check_mask(const std::string& what, bool masked, int64_t N, const int64_t* mask_ptr, const int32_t* mask_cols) {
+  if (!masked) return TAGREC_OK;
+  TAGREC_REQUIRE(mask_ptr && mask_cols, what + ": null mask_ptr / mask_cols (an empty list set still has its row pointers)");
+  if (N > INT32_MAX) return fail(TAGREC_E_UNSUPPORTED, what + ": the masked form takes N <= 2^31 - 1, got " + std::to_string(N));
+  return TAGREC_OK;
+}
+
+static int cat_fwd(const std::string& what, bool masked, const float* Q, int64_t ldq, const int64_t* qrow, const float* T,
+                   int64_t ldt, int64_t N, int D, const int64_t* target, const int64_t* mask_ptr, const int32_t* mask_cols,
+                   const float* Qreg, const float* Treg, int64_t ldreg, int Dreg, int64_t B, float temperature, int n_split,
+                   void* workspace, int64_t workspace_bytes, float* lse, float* zt, float* loss_out, void* stream) {
+  if (int rc = check_shape(what.c_str(), B, N, D, ldq, ldt)) return rc;
+  TAGREC_REQUIRE(Q && T && target && workspace && lse && zt && loss_out, what + ": null pointer");
+  if (int rc = cat_check_mask(what, masked, N, mask_ptr, mask_cols)) return rc;
+  TAGREC_REQUIRE((Qreg == nullptr) == (Treg == nullptr), what + ": Qreg/Treg must both be given or both null");
+  TAGREC_REQUIRE(!Qreg || (Dreg >= 1 && ldreg >= Dreg), what + ": bad reg shape");
+  if (int rc = check_temperature(what, temperature)) return rc;
   int ns = 0;
-  if (int rc = resolve_splits("catsoftmax_fwd", B, N, n_split, &ns)) return rc;
-  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_fwd: the workspace is too small");
+  if (int rc = resolve_splits(what.c_str(), B, N, n_split, &ns)) return rc;
+  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), what + ": the workspace is too small");
   CatArgs a = {};
   fill_args(a, Q, ldq, qrow, T, ldt, N, D, target, B, temperature, ns);
+  a.mask_ptr = mask_ptr; a.mask_cols = mask_cols;
   float* ws = static_cast<float*>(workspace);
   a.pm = ws;
   a.ps = ws + static_cast<int64_t>(ns) * B;
@@ -326,8 +481,11 @@ extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nf = pick_nf(D);
   const dim3 grid(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
-  const size_t lds = lds_bytes(16 * nf);
-  if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_fwd_kernel<decltype(n)::value>>(grid, lds, a, s); })) return rc;
+  const size_t lds = lds_bytes(16 * nf, masked);
+  if (int rc = dispatch_nf(nf, [&](auto n) {
+        constexpr int NF = decltype(n)::value;
+        return masked ? launch_lds<CatArgs, cat_fwd_masked_kernel<NF>>(grid, lds, a, s) : launch_lds<CatArgs, cat_fwd_kernel<NF>>(grid, lds, a, s);
+      })) return rc;
   RegArgs x = {Qreg, Treg, qrow, target, ldreg, N, Dreg};
   const int64_t blocks = combine_blocks(B);
   cat_combine_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, s>>>(a.pm, a.ps, ns, B, zt, x, lse, partials);
@@ -337,34 +495,42 @@ extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int6
   return TAGREC_OK;
 }
 
-extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
-                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
-                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
-                                         int64_t workspace_bytes, const float* lse, const float* g, float* dT, int64_t lddt,
-                                         float* dQ, float* dQreg, float* dTreg, void* stream) {
-  if (int rc = check_shape("catsoftmax_bwd", B, N, D, ldq, ldt)) return rc;
-  TAGREC_REQUIRE(Q && T && target && workspace && lse, "catsoftmax_bwd: null pointer");
-  TAGREC_REQUIRE((dT == nullptr) == (dQ == nullptr), "catsoftmax_bwd: dT/dQ must both be given or both null (the L2 part only)");
-  TAGREC_REQUIRE(dT || dQreg, "catsoftmax_bwd: nothing to write");
-  TAGREC_REQUIRE(!dT || lddt >= D, "catsoftmax_bwd: row stride of dT below D");
-  TAGREC_REQUIRE((dQreg == nullptr) == (dTreg == nullptr), "catsoftmax_bwd: dQreg/dTreg must both be given or both null");
-  TAGREC_REQUIRE(!dQreg || (Qreg && Treg && Dreg >= 1 && ldreg >= Dreg), "catsoftmax_bwd: bad reg arguments");
-  if (int rc = check_temperature("catsoftmax_bwd", temperature)) return rc;
+static int cat_bwd(const std::string& what, bool masked, const float* Q, int64_t ldq, const int64_t* qrow, const float* T,
+                   int64_t ldt, int64_t N, int D, const int64_t* target, const int64_t* mask_ptr, const int32_t* mask_cols,
+                   const float* Qreg, const float* Treg, int64_t ldreg, int Dreg, int64_t B, float temperature, int n_split,
+                   void* workspace, int64_t workspace_bytes, const float* lse, const float* g, float* dT, int64_t lddt, float* dQ,
+                   float* dQreg, float* dTreg, void* stream) {
+  if (int rc = check_shape(what.c_str(), B, N, D, ldq, ldt)) return rc;
+  TAGREC_REQUIRE(Q && T && target && workspace && lse, what + ": null pointer");
+  if (int rc = cat_check_mask(what, masked, N, mask_ptr, mask_cols)) return rc;
+  TAGREC_REQUIRE((dT == nullptr) == (dQ == nullptr), what + ": dT/dQ must both be given or both null (the L2 part only)");
+  TAGREC_REQUIRE(dT || dQreg, what + ": nothing to write");
+  TAGREC_REQUIRE(!dT || lddt >= D, what + ": row stride of dT below D");
+  TAGREC_REQUIRE((dQreg == nullptr) == (dTreg == nullptr), what + ": dQreg/dTreg must both be given or both null");
+  TAGREC_REQUIRE(!dQreg || (Qreg && Treg && Dreg >= 1 && ldreg >= Dreg), what + ": bad reg arguments");
+  if (int rc = check_temperature(what, temperature)) return rc;
   int ns = 0;
-  if (int rc = resolve_splits("catsoftmax_bwd", B, N, n_split, &ns)) return rc;
-  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), "catsoftmax_bwd: the workspace is too small");
+  if (int rc = resolve_splits(what.c_str(), B, N, n_split, &ns)) return rc;
+  TAGREC_REQUIRE(workspace_bytes >= 4 * workspace_floats(B, D, ns), what + ": the workspace is too small");
   CatArgs a = {};
   fill_args(a, Q, ldq, qrow, T, ldt, N, D, target, B, temperature, ns);
+  a.mask_ptr = mask_ptr; a.mask_cols = mask_cols;
   a.lse = lse; a.g = g; a.dT = dT; a.lddt = lddt;
   a.dQpart = ns == 1 ? dQ : static_cast<float*>(workspace);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nf = pick_nf(D);
-  const size_t lds = lds_bytes(16 * nf);
+  const size_t lds = lds_bytes(16 * nf, masked);
   if (dT) {
     const dim3 grid_t(static_cast<unsigned>(col_tiles(N)));
-    if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_dt_kernel<decltype(n)::value>>(grid_t, lds, a, s); })) return rc;
+    if (int rc = dispatch_nf(nf, [&](auto n) {
+          constexpr int NF = decltype(n)::value;
+          return masked ? launch_lds<CatArgs, cat_dt_masked_kernel<NF>>(grid_t, lds, a, s) : launch_lds<CatArgs, cat_dt_kernel<NF>>(grid_t, lds, a, s);
+        })) return rc;
     const dim3 grid_q(static_cast<unsigned>((B + kTile - 1) / kTile), static_cast<unsigned>(ns));
-    if (int rc = dispatch_nf(nf, [&](auto n) { return launch_lds<CatArgs, cat_dq_kernel<decltype(n)::value>>(grid_q, lds, a, s); })) return rc;
+    if (int rc = dispatch_nf(nf, [&](auto n) {
+          constexpr int NF = decltype(n)::value;
+          return masked ? launch_lds<CatArgs, cat_dq_masked_kernel<NF>>(grid_q, lds, a, s) : launch_lds<CatArgs, cat_dq_kernel<NF>>(grid_q, lds, a, s);
+        })) return rc;
   }
   if (dT && ns > 1) {
     const int64_t BD = B * D;
@@ -378,4 +544,40 @@ extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int6
     TAGREC_LAUNCH_CHECK();
   }
   return TAGREC_OK;
+}
+
+extern "C" int tagrec_catsoftmax_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                         int64_t workspace_bytes, float* lse, float* zt, float* loss_out, void* stream) {
+  return cat_fwd("catsoftmax_fwd", false, Q, ldq, qrow, T, ldt, N, D, target, nullptr, nullptr, Qreg, Treg, ldreg, Dreg, B,
+                 temperature, n_split, workspace, workspace_bytes, lse, zt, loss_out, stream);
+}
+
+extern "C" int tagrec_catsoftmax_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt, int64_t N,
+                                         int D, const int64_t* target, const float* Qreg, const float* Treg, int64_t ldreg,
+                                         int Dreg, int64_t B, float temperature, int n_split, void* workspace,
+                                         int64_t workspace_bytes, const float* lse, const float* g, float* dT, int64_t lddt,
+                                         float* dQ, float* dQreg, float* dTreg, void* stream) {
+  return cat_bwd("catsoftmax_bwd", false, Q, ldq, qrow, T, ldt, N, D, target, nullptr, nullptr, Qreg, Treg, ldreg, Dreg, B,
+                 temperature, n_split, workspace, workspace_bytes, lse, g, dT, lddt, dQ, dQreg, dTreg, stream);
+}
+
+extern "C" int tagrec_catsoftmax_masked_fwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt,
+                                                int64_t N, int D, const int64_t* target, const float* Qreg, const float* Treg,
+                                                int64_t ldreg, int Dreg, int64_t B, float temperature, int n_split,
+                                                void* workspace, int64_t workspace_bytes, float* lse, float* zt, float* loss_out,
+                                                void* stream, const int64_t* mask_ptr, const int32_t* mask_cols) {
+  return cat_fwd("catsoftmax_masked_fwd", true, Q, ldq, qrow, T, ldt, N, D, target, mask_ptr, mask_cols, Qreg, Treg, ldreg, Dreg,
+                 B, temperature, n_split, workspace, workspace_bytes, lse, zt, loss_out, stream);
+}
+
+extern "C" int tagrec_catsoftmax_masked_bwd_f32(const float* Q, int64_t ldq, const int64_t* qrow, const float* T, int64_t ldt,
+                                                int64_t N, int D, const int64_t* target, const float* Qreg, const float* Treg,
+                                                int64_t ldreg, int Dreg, int64_t B, float temperature, int n_split,
+                                                void* workspace, int64_t workspace_bytes, const float* lse, const float* g,
+                                                float* dT, int64_t lddt, float* dQ, float* dQreg, float* dTreg, void* stream,
+                                                const int64_t* mask_ptr, const int32_t* mask_cols) {
+  return cat_bwd("catsoftmax_masked_bwd", true, Q, ldq, qrow, T, ldt, N, D, target, mask_ptr, mask_cols, Qreg, Treg, ldreg, Dreg,
+                 B, temperature, n_split, workspace, workspace_bytes, lse, g, dT, lddt, dQ, dQreg, dTreg, stream);
 }

@@ -237,18 +237,38 @@ def in_batch_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, item_logq=None, plan
     return out[0], out[1]
 
 
+def user_positives_csr(edge_index, n_user, n_item, device):
+    """The train items of every user as a CSR for the masked catalogue softmax (catalogue_mask="train_positives"):
+    -> (ptr int64 [n_user + 1], items int32), a user's items ascending and unique (duplicate edges fold, the order of the
+    edges does not matter), a user without edges has an empty row.  edge_index: [E, 2] = (user, item), a tensor or an array;
+    built once on the host (numpy), as `item_logq_table` is, then moved to `device`."""
+    import numpy as np
+    edges = edge_index.cpu().numpy() if torch.is_tensor(edge_index) else np.asarray(edge_index)
+    edges = edges.reshape(-1, 2).astype(np.int64)
+    if n_item > 2 ** 31 - 1:
+        raise _lib.TagrecError(f"user_positives_csr: the item ids are kept as int32, n_item={n_item} does not fit")
+    users, items = edges[:, 0], edges[:, 1]
+    if edges.shape[0] and (users.min() < 0 or users.max() >= n_user or items.min() < 0 or items.max() >= n_item):
+        raise _lib.TagrecError(f"user_positives_csr: an edge lies outside [0, {n_user}) x [0, {n_item})")
+    keys = np.unique(users * np.int64(n_item) + items)                      # sorted by (user, item), duplicates gone
+    ptr = np.zeros(n_user + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys // n_item, minlength=n_user), out=ptr[1:])
+    return torch.from_numpy(ptr).to(device), torch.from_numpy((keys % n_item).astype(np.int32)).to(device)
+
+
 class CatalogueRoute(NamedTuple):
     """What a fused step is handed in place of `rank_route`'s (K, temperature) when the model has softmax_over="catalogue"."""
     temperature: float
+    positives: Optional[tuple] = None      # `user_positives_csr`'s pair (catalogue_mask="train_positives"), or None: no mask
 
 
-def catalogue_route(model, batch, temperature):
+def catalogue_route(model, batch, temperature, positives=None):
     """A model with softmax_over="catalogue" takes [B, 2] = (user, positive) batches; any other width is refused.
     -> the `CatalogueRoute` its step takes."""
     if batch.dim() != 2 or batch.shape[1] != 2:
         raise _lib.TagrecError(f"{model}: a batch of shape {tuple(batch.shape)} does not fit softmax_over=\"catalogue\" "
                                "(expected [B, 2] = user, positive; every item of the catalogue is a column of the softmax)")
-    return CatalogueRoute(float(temperature))
+    return CatalogueRoute(float(temperature), positives)
 
 
 class _CatalogueLoss(torch.autograd.Function):
@@ -267,9 +287,9 @@ class _CatalogueLoss(torch.autograd.Function):
         urow, target = stage.ids(pairs)
         has_reg = Ureg is not None
         same = has_reg and Ureg.data_ptr() == U.data_ptr() and Ireg.data_ptr() == I.data_ptr() and Ureg.shape == U.shape
-        res, lse, _ = rowops.catsoftmax_fwd(U, I, target, stage.temperature, urow, Ureg, Ireg)
+        res, lse, _ = rowops.catsoftmax_fwd(U, I, target, stage.temperature, urow, Ureg, Ireg, mask=stage.positives)
         ctx.save_for_backward(U, I, Ureg if has_reg else U.new_empty(0), Ireg if has_reg else U.new_empty(0), urow, target, lse)
-        ctx.tau, ctx.has_reg, ctx.same, ctx.plans = stage.temperature, has_reg, same, plans
+        ctx.tau, ctx.has_reg, ctx.same, ctx.plans, ctx.mask = stage.temperature, has_reg, same, plans, stage.positives
         return res
 
     @staticmethod
@@ -283,7 +303,7 @@ class _CatalogueLoss(torch.autograd.Function):
             dUr, dIr = torch.empty(2, B, Ureg.shape[1], dtype=torch.float32, device=U.device)
         else:
             Ureg = Ireg = None
-        dQ = rowops.catsoftmax_bwd(U, I, target, ctx.tau, lse, g, dI, None, urow, Ureg, Ireg, dUr, dIr)
+        dQ = rowops.catsoftmax_bwd(U, I, target, ctx.tau, lse, g, dI, None, urow, Ureg, Ireg, dUr, dIr, mask=ctx.mask)
         dU = rowops.fold_rows(torch.zeros(U.shape, dtype=torch.float32, device=U.device), urow, dQ, pu)
         if not ctx.has_reg:
             return dU, dI, None, None, None, None, None
@@ -296,14 +316,17 @@ class _CatalogueLoss(torch.autograd.Function):
         return dU, dI, dUreg, dIreg, None, None, None
 
 
-def catalogue_softmax_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, plans=None):
+def catalogue_softmax_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, plans=None, positives=None):
     """(mul_loss, l2reg_loss) of a [B, 2] batch (user, positive) under the full softmax: EVERY row of I is a column,
-    mul_loss = mean_b [logsumexp_n(u_b . i_n / temperature) - u_b . i_{p_b} / temperature]; nothing is sampled, masked or
-    corrected.  l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg (None: 0).  The B x n_item logits are never
+    mul_loss = mean_b [logsumexp_n(u_b . i_n / temperature) - u_b . i_{p_b} / temperature]; nothing is sampled or corrected,
+    and nothing is masked unless `positives` is given.  l2reg_loss = 0.5 (|u|^2 + |p|^2) / B on the rows of Ureg / Ireg (None: 0).  The B x n_item logits are never
     stored; the gradient of I is dense.  The ids must lie inside the tables (not checked: that would take a host read).
     plans (`in_batch_plans`): the compact user and L2 gradients are folded onto the tables in a fixed order (the same bits
-    every run) instead of by `index_add_`."""
-    out = stage_loss(S.Catalogue(float(temperature)), U, I, Ureg, Ireg, pairs, plans)
+    every run) instead of by `index_add_`.
+    positives (`user_positives_csr`'s pair over the rows of U; None: no mask): a pair (u, p) leaves u's OTHER listed items out
+    of its softmax -- they are not negatives -- and their gradient coefficient is exactly 0; p itself stays a column whether
+    or not it is listed."""
+    out = stage_loss(S.Catalogue(float(temperature), positives), U, I, Ureg, Ireg, pairs, plans)
     return out[0], out[1]
 
 

@@ -17,7 +17,7 @@ import torch
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, StepWorkspace, _Token, fused_last_hop, step_buffer, xavier_tables  # noqa: F401  (xavier_tables re-exported)
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking, check_softmax_over
+from .config import CFG as _GLOBAL_CFG, check_catalogue_mask, check_negatives, check_ranking, check_softmax_over
 from .graph import EdgeDropView, Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -340,6 +340,9 @@ class LightGCN(FusedStepModel):
                                                                   self.split_adj_k, self.device)
         # the logQ correction of in-batch negatives: log(train degree / train edges) per item, fixed at construction
         self.item_logq = H.item_logq_table(data.edge_index["train"], self.num_list[1], self.device) if self.in_batch_logq else None
+        # catalogue_mask="train_positives": every user's train items as a CSR, fixed at construction (rowops.catsoftmax_* mask)
+        self.positives = H.user_positives_csr(data.edge_index["train"], self.num_list[0], self.num_list[1], self.device) \
+            if self.mask_positives else None
 
     def _config(self, config):
         self.dim_latent = config["dim_latent"]
@@ -354,6 +357,8 @@ class LightGCN(FusedStepModel):
         self.in_batch, self.in_batch_logq = check_negatives(config)
         # softmax_over="catalogue": [B, 2] batches, every item is a column of the user's softmax (rowops.catsoftmax_*)
         self.over_catalogue = check_softmax_over(config)
+        # catalogue_mask="train_positives": the user's other train items leave the row's softmax (help.user_positives_csr)
+        self.mask_positives = check_catalogue_mask(config)
         self.use_tag = config["use_tag"]
         self.message_drop_list = config["message_drop_list"]
         self.node_drop = config["node_drop"]
@@ -418,7 +423,7 @@ class LightGCN(FusedStepModel):
         if self.in_batch:
             return H.in_batch_route(type(self).__name__, batch_data, self.loss_temperature, self.item_logq)
         if self.over_catalogue:
-            return H.catalogue_route(type(self).__name__, batch_data, self.loss_temperature)
+            return H.catalogue_route(type(self).__name__, batch_data, self.loss_temperature, self.positives)
         return H.rank_route(type(self).__name__, batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
 
     def loss(self, batch_data):

@@ -151,12 +151,13 @@ class Au(_Stage):
 
 class Catalogue(_Stage):
     """[B, 2] = (user, positive) under the full softmax: every item of the catalogue is a column of the user's softmax
-    (`rowops.catsoftmax_fwd` / `catsoftmax_bwd`; the B x n_item logits are never stored).  Nothing is sampled or masked."""
+    (`rowops.catsoftmax_fwd` / `catsoftmax_bwd`; the B x n_item logits are never stored).  Nothing is sampled.
+    positives (`help.user_positives_csr`'s pair, or None: no mask): the user's other train items leave the row's softmax."""
     name, batch_word = "catalogue_softmax_loss", "pairs"
     grads_zeroed = on_tables = dense = True      # the dense store covers the item block only: the rest of d_out arrives zeroed
 
-    def __init__(self, temperature):
-        self.temperature = temperature
+    def __init__(self, temperature, positives=None):
+        self.temperature, self.positives = temperature, positives
 
     def check(self, name, batch):
         if batch.dim() != 2 or batch.shape[1] != 2:
@@ -168,7 +169,8 @@ class Catalogue(_Stage):
         self._cut = lambda t: (None, None) if t is None else (t[:n_user], t[n_user:n_user + n_item])
         self.n_user = n_user
         self.urow, self.target = self.ids(batch)
-        res, self.lse, _ = rowops.catsoftmax_fwd(*self._cut(out), self.target, self.temperature, self.urow, *self._cut(ego))
+        res, self.lse, _ = rowops.catsoftmax_fwd(*self._cut(out), self.target, self.temperature, self.urow, *self._cut(ego),
+                                                 mask=self.positives)
         return res
 
     def bwd_on_tables(self, out, ego, g, d_out, d_ego, plan=None, what=None):
@@ -177,7 +179,9 @@ class Catalogue(_Stage):
         last -- d_ego may be d_out.  d_out None: the L2 part only, added to what d_ego holds.
         plan (the `row_list_plan` of `rows`, users then items): both folds run in a fixed order, no float atomics."""
         B, D = self.urow.shape[0], out.shape[1]
-        kw = {} if what is None else {"what": f"catsoftmax_bwd({what})"}
+        kw = {"mask": self.positives}
+        if what is not None:
+            kw["what"] = f"catsoftmax_bwd({what})"
         d_e = dQr = dTr = None
         if ego is not None and d_ego is not None:
             d_e = torch.empty(2 * B, ego.shape[1], dtype=torch.float32, device=out.device)

@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib, help as H, rowops
 from .base import FusedStepModel, fused_last_hop, scatter_rows as _scatter_rows
 from .base import layer_seed as _layer_seed
-from .config import CFG as _GLOBAL_CFG, check_negatives, check_ranking, check_softmax_over
+from .config import CFG as _GLOBAL_CFG, check_catalogue_mask, check_negatives, check_ranking, check_softmax_over
 from .graph import Graph, creat_adj
 from .rowops import VEC_WIDTHS
 from .train import fused_optimizer
@@ -403,6 +403,9 @@ class NGCF(FusedStepModel):
                                                                   self.split_adj_k, self.device)
         # the logQ correction of in-batch negatives: log(train degree / train edges) per item, fixed at construction
         self.item_logq = H.item_logq_table(data.edge_index["train"], self.num_list[1], self.device) if self.in_batch_logq else None
+        # catalogue_mask="train_positives": every user's train items as a CSR, fixed at construction (rowops.catsoftmax_* mask)
+        self.positives = H.user_positives_csr(data.edge_index["train"], self.num_list[0], self.num_list[1], self.device) \
+            if self.mask_positives else None
 
     def _config(self, config):
         self.dim_latent = config["dim_latent"]
@@ -420,6 +423,8 @@ class NGCF(FusedStepModel):
         self.in_batch, self.in_batch_logq = check_negatives(config)
         # softmax_over="catalogue": [B, 2] batches, every item is a column of the user's softmax (rowops.catsoftmax_*)
         self.over_catalogue = check_softmax_over(config)
+        # catalogue_mask="train_positives": the user's other train items leave the row's softmax (help.user_positives_csr)
+        self.mask_positives = check_catalogue_mask(config)
         self.use_tag = config["use_tag"]
         self.drop_seed = config.get("seed", 2020)
         # one step = a pure function of its inputs: batch gradients are folded in a fixed order (rowops.scatter_rows_ordered)
@@ -461,7 +466,7 @@ class NGCF(FusedStepModel):
         if self.in_batch:
             route = H.in_batch_route("NGCF", batch_data, self.loss_temperature, self.item_logq)
         elif self.over_catalogue:
-            route = H.catalogue_route("NGCF", batch_data, self.loss_temperature)
+            route = H.catalogue_route("NGCF", batch_data, self.loss_temperature, self.positives)
         else:
             route = H.rank_route("NGCF", batch_data, self.n_negatives, self.loss_func, self.loss_temperature)
         stage = H.stage_for(route, H.loss_kind_id(self.loss_func))

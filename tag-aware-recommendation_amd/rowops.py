@@ -364,27 +364,61 @@ def _catsoftmax_args(what, Q, T, target, qrow, Qreg, Treg, n_split, workspace):
     return B, N, D, ldreg, dreg, workspace
 
 
-def catsoftmax_fwd(Q, T, target, temperature, qrow=None, Qreg=None, Treg=None, n_split=0, workspace=None):
+_NO_COLS = {}        # device -> the one int32 that stands for the ids of an all-empty CSR (never read: every row is empty)
+
+
+def _catsoftmax_mask(what, mask, Q, N):
+    """The (ptr, cols) pair of the masked form after the checks that need no host read: ptr int64 [rows of Q + 1], cols int32,
+    both contiguous and on Q's device.  Sortedness and the ids are NOT checked (that would take a host read): an unsorted list
+    gives an unspecified mask, but the kernels read nothing outside [ptr[r], ptr[r + 1]) of cols."""
+    if not isinstance(mask, (tuple, list)) or len(mask) != 2 or not all(isinstance(t, torch.Tensor) for t in mask):
+        raise _lib.TagrecError(f"{what}: mask must be a pair of tensors (ptr, cols), got {type(mask).__name__}")
+    ptr, cols = mask
+    if ptr.dtype != torch.int64 or ptr.dim() != 1 or not ptr.is_contiguous() or ptr.device != Q.device \
+            or ptr.numel() != Q.shape[0] + 1:
+        raise _lib.TagrecError(f"{what}: mask ptr must be a contiguous int64 tensor of shape [{Q.shape[0] + 1}] (the rows of Q "
+                               f"+ 1) on {Q.device}, got {ptr.dtype} {tuple(ptr.shape)} on {ptr.device}")
+    if cols.dtype != torch.int32 or cols.dim() != 1 or not cols.is_contiguous() or cols.device != Q.device:
+        raise _lib.TagrecError(f"{what}: mask cols must be a contiguous 1-d int32 tensor on {Q.device}, got {cols.dtype} "
+                               f"{tuple(cols.shape)} on {cols.device}")
+    if N > 2 ** 31 - 1:
+        raise _lib.TagrecError(f"{what}: the masked form takes N <= 2^31 - 1 columns (int32 ids), got {N}")
+    if cols.numel() == 0:                        # an empty tensor has no address: the library wants a pointer all the same
+        cols = _NO_COLS.get(Q.device)
+        if cols is None:                         # one per device, kept: nothing is allocated inside a later graph capture
+            cols = _NO_COLS[Q.device] = torch.zeros(1, dtype=torch.int32, device=Q.device)
+    return ptr, cols
+
+
+def catsoftmax_fwd(Q, T, target, temperature, qrow=None, Qreg=None, Treg=None, n_split=0, workspace=None, mask=None):
     """Softmax cross-entropy of B rows against EVERY row of T: z_bn = Q[qrow[b]] . T[n] / temperature (qrow None: row b),
     loss_b = logsumexp_n z_bn - z_{b, target[b]}; Qreg / Treg (read at qrow / target; None: no L2 term) the L2 rows.
     -> (res = [mean_b loss_b, l2reg_loss (unweighted)], lse [B] for `catsoftmax_bwd`, zt [B] the target logits).
     The B x N logits are never stored.  n_split: column ranges the walk is cut into (0: `catsoftmax_splits`).  target must lie
-    in [0, N) and qrow in the rows of Q: neither is checked (the kernels keep their reads inside the operands regardless)."""
-    B, N, D, ldreg, dreg, workspace = _catsoftmax_args("catsoftmax_fwd", Q, T, target, qrow, Qreg, Treg, n_split, workspace)
+    in [0, N) and qrow in the rows of Q: neither is checked (the kernels keep their reads inside the operands regardless).
+    mask = (ptr int64 [rows of Q + 1], cols int32): a CSR over the rows of Q, ascending and unique within a row; row b leaves
+    the columns of row qrow[b] (b without qrow) out of its softmax, all but target[b] itself (`_catsoftmax_mask` for what is
+    checked).  None: the unmasked kernels, untouched."""
+    what = "catsoftmax_fwd"
+    B, N, D, ldreg, dreg, workspace = _catsoftmax_args(what, Q, T, target, qrow, Qreg, Treg, n_split, workspace)
     small = torch.empty(2 * B + 2, dtype=torch.float32, device=Q.device)         # lse | zt | res
     lse, zt, res = small[:B], small[B:2 * B], small[2 * B:]
-    check(load().tagrec_catsoftmax_fwd_f32(Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B,
-                                           float(temperature), n_split, workspace, workspace.numel(), lse, zt, res, stream_ptr()),
-          "catsoftmax_fwd")
+    args = (Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B, float(temperature), n_split, workspace,
+            workspace.numel(), lse, zt, res, stream_ptr())
+    if mask is None:
+        check(load().tagrec_catsoftmax_fwd_f32(*args), what)
+    else:
+        check(load().tagrec_catsoftmax_masked_fwd_f32(*args, *_catsoftmax_mask(what, mask, Q, N)), what)
     return res, lse, zt
 
 
 def catsoftmax_bwd(Q, T, target, temperature, lse, g, dT, dQ=None, qrow=None, Qreg=None, Treg=None, dQreg=None, dTreg=None,
-                   n_split=0, workspace=None, what="catsoftmax_bwd"):
+                   n_split=0, workspace=None, what="catsoftmax_bwd", mask=None):
     """STORES the gradients of `catsoftmax_fwd`'s two loss parts (g = their upstream gradients, two floats; None: both 1):
     every row of the dense dT [N, D] (may be a strided view) and of the compact dQ [B, D] (None: allocated) -- no atomics, the
     old contents are not read, the same bits for one (B, N, D, n_split).  dQreg / dTreg [B, Dreg] (both None: not written):
     the compact L2 gradients of the rows Qreg[qrow] / Treg[target]; dT = dQ = None: they alone.  Folding repeated qrow ids / targets is the caller's.
+    mask: the forward's (`catsoftmax_fwd`); an excluded column's coefficient is exactly 0.
     -> dQ."""
     B, N, D, ldreg, dreg, workspace = _catsoftmax_args(what, Q, T, target, qrow, Qreg, Treg, n_split, workspace)
     g = None if g is None else g.contiguous()
@@ -406,9 +440,12 @@ def catsoftmax_bwd(Q, T, target, temperature, lse, g, dT, dQ=None, qrow=None, Qr
     for nm, t in (("dQreg", dQreg), ("dTreg", dTreg)):
         if t is not None and (t.shape != (B, dreg) or t.dtype != torch.float32 or not t.is_contiguous()):
             raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must be a contiguous float32 [{B}, {dreg}] tensor")
-    check(load().tagrec_catsoftmax_bwd_f32(Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B,
-                                           float(temperature), n_split, workspace, workspace.numel(), lse, g, dT,
-                                           0 if dT is None else _row_ld(dT), dQ, dQreg, dTreg, stream_ptr()), what)
+    args = (Q, _row_ld(Q), qrow, T, _row_ld(T), N, D, target, Qreg, Treg, ldreg, dreg, B, float(temperature), n_split, workspace,
+            workspace.numel(), lse, g, dT, 0 if dT is None else _row_ld(dT), dQ, dQreg, dTreg, stream_ptr())
+    if mask is None:
+        check(load().tagrec_catsoftmax_bwd_f32(*args), what)
+    else:
+        check(load().tagrec_catsoftmax_masked_bwd_f32(*args, *_catsoftmax_mask(what, mask, Q, N)), what)
     return dQ
 
 

@@ -1,7 +1,7 @@
 """Time the catalogue softmax kernels (tagrec_catsoftmax_fwd_f32 / tagrec_catsoftmax_bwd_f32, csrc/catsoftmax.hip) against
 the materialised torch form and the eval kernel on the same table, and the LightGCN step that uses them, at the C2 shape.
 
-Usage: python tools/catsoftmax_microbench.py [--scale 1.0] [--rounds 9] [--steps 10]      (needs a GPU)
+Usage: python tools/catsoftmax_microbench.py [--scale 1.0] [--rounds 9] [--steps 10] [--mask-len L [--mask-only]]   (needs a GPU)
   Kernels: D = 64, N = 1 M items (times --scale), B = 512 and 2 048 users read through qrow from a 1 M-row table, L2 on the
   score tables.  "fused" = rowops.catsoftmax_fwd + catsoftmax_bwd (forward, combine, the dense dT, the split dQ and its sum),
   "fwd" the forward alone.  "torch" = the materialised form on the same GPU: U[u] @ I.T / tau, F.cross_entropy, autograd --
@@ -16,6 +16,12 @@ Usage: python tools/catsoftmax_microbench.py [--scale 1.0] [--rounds 9] [--steps
   softmax_over = "catalogue" next to the default triplet step and to the same triplet step with restrict_forward = False (the
   catalogue step is an all-rows step plus the loss stage), in the same process on the same graph: `--steps` steps between
   synchronisations per measurement, the variants interleaved over the rounds.
+  Mask (--mask-len L > 0): the masked entry points (mask=(ptr, cols)) next to the unmasked ones at B = 512, the forward and
+  the backward (dT, dQ, its sum, the L2 rows) each as one call, interleaved as above.  Every row of the 1 M-row user table
+  gets a list of exactly L columns, ascending and unique by construction: column j of a row is drawn uniformly from the
+  j-th of L equal strata of [0, N) (L = 50 is the C2 mean: 50 M train edges over 1 M users).  --mask-only: this leg alone.
+  The split of the backward into dT and dQ is not visible to device events around one call: take it from a kernel trace of
+  `--mask-only` (the kernels are cat_dt_kernel / cat_dt_masked_kernel, cat_dq_kernel / cat_dq_masked_kernel).
 Prints one JSON line per measurement."""
 import argparse
 import json
@@ -99,6 +105,42 @@ def kernel_variants(N):
     return out, notes
 
 
+def stratified_lists(rows, N, L, g):
+    """(ptr int64 [rows + 1], cols int32 [rows L]): L columns per row, ascending and unique: one uniform draw per stratum."""
+    width = N // L
+    assert width >= 1, "more list entries than columns"
+    cols = torch.arange(L, device=dev, dtype=torch.int64)[None, :] * width + torch.randint(0, width, (rows, L), device=dev, generator=g)
+    return torch.arange(rows + 1, device=dev, dtype=torch.int64) * L, cols.to(torch.int32).reshape(-1)
+
+
+def mask_variants(N, L, B=512):
+    g = torch.Generator(device=dev).manual_seed(1)
+    U, I = torch.randn(N, D, device=dev, generator=g) * 0.3, torch.randn(N, D, device=dev, generator=g) * 0.3
+    dI = torch.empty_like(I)
+    up = torch.tensor([1.0, 1e-3], device=dev)
+    urow = torch.randint(0, N, (B,), device=dev, generator=g)
+    mask = stratified_lists(N, N, L, g)
+    # a train pair: the target is one of the user's own listed items (it stays live)
+    pick = torch.randint(0, L, (B,), device=dev, generator=g)
+    target = mask[1][urow * L + pick].to(torch.int64)
+    ws = torch.empty(rowops.catsoftmax_workspace(B, N, D), dtype=torch.uint8, device=dev)
+    dQ, dQr, dTr = (torch.empty(B, D, device=dev) for _ in range(3))
+    out = {}
+    for name, m in (("unmasked", None), ("masked", mask)):
+        _, lse, _ = rowops.catsoftmax_fwd(U, I, target, TAU, urow, U, I, 0, ws, mask=m)
+
+        def fwd(m=m):
+            return rowops.catsoftmax_fwd(U, I, target, TAU, urow, U, I, 0, ws, mask=m)
+
+        def bwd(m=m, lse=lse):
+            rowops.catsoftmax_bwd(U, I, target, TAU, lse, up, dI, dQ, urow, U, I, dQr, dTr, 0, ws, mask=m)
+        out[f"fwd_{name}_B{B}"], out[f"bwd_{name}_B{B}"] = fwd, bwd
+    note = {"leg": "mask", "B": B, "N": N, "list_len": L, "lists": "one uniform draw from each of L equal strata of [0, N), every "
+            "row of the user table; the target is one of the row's listed items", "n_split": rowops.catsoftmax_splits(B, N, D),
+            "list_MB": round(mask[1].numel() * 4 / 1e6, 1)}
+    return out, note
+
+
 def step_variants(scale, steps, B=512):
     nu = ni = max(int(1_000_000 * scale), 2000)
     ne = max(int(50_000_000 * scale), 40000)
@@ -136,9 +178,26 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--steps", type=int, default=10, help="steps per measurement of the step leg")
     ap.add_argument("--no-step", action="store_true", help="kernels only")
+    ap.add_argument("--mask-len", type=int, default=0, help="> 0: time the masked entry points with lists of this length per row")
+    ap.add_argument("--mask-only", action="store_true", help="the mask leg alone (needs --mask-len)")
     a = ap.parse_args()
     N = max(int((1 << 20) * a.scale), 2048)
     print(json.dumps({"D": D, "tau": TAU, "N": N, "device": torch.cuda.get_device_name(0), "rounds": a.rounds}), flush=True)
+    if a.mask_only and a.mask_len <= 0:
+        ap.error("--mask-only needs --mask-len")
+    if a.mask_len > 0:
+        variants, note = mask_variants(N, a.mask_len)
+        print(json.dumps(note), flush=True)
+        res = interleaved(variants, a.rounds, 2)
+        for k, (med, lo, hi) in res.items():
+            line = {"leg": "mask", "variant": k, "median_ms": round(med, 4), "min_ms": round(lo, 4), "max_ms": round(hi, 4)}
+            if "_masked_" in k:
+                line["masked_over_unmasked"] = round(med / res[k.replace("_masked_", "_unmasked_")][0], 4)
+            print(json.dumps(line), flush=True)
+        del variants
+        torch.cuda.empty_cache()
+        if a.mask_only:
+            sys.exit(0)
     variants, notes = kernel_variants(N)
     for nline in notes:
         print(json.dumps(nline), flush=True)

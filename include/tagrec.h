@@ -356,6 +356,9 @@ int tagrec_bpr_fwd_f32(const float* U, const float* I, int64_t ld, int D,
  *   dU[u] += g0*coef/B * (I[n]-I[p]);  dI[p] -= g0*coef/B * U[u];  dI[n] += g0*coef/B * U[u]
  *   dXreg[row] += g1 * reg / B * Xreg[row]     for the three rows of every triplet
  * g = device pointer to two floats (upstream gradients of the two loss parts) or NULL for (1,1).
+ * Where the L2 part reads the main tables and shares their gradient buffers (Ureg == U, Ireg == I, dUreg == dU,
+ * dIreg == dI, same stride and width) a slot adds its two terms as ONE value: a row that two triplets name is then a
+ * sum of two additions, the same bits in either order.
  * Callers zero the gradient buffers.  dU = dI = NULL runs the L2 part only (so it can be added
  * after the propagation backward has overwritten the ego gradient). */
 int tagrec_bpr_bwd_f32(const float* U, const float* I, int64_t ld, int D,

@@ -652,6 +652,7 @@ extern "C" int tagrec_ngcf_wgrad_rows_f32(const float* Nn, const float* X, const
                                           int Din, int Dout, float* dW1p, float* dW2p, float* workspace,
                                           int64_t workspace_floats, const uint8_t* row_mask, void* stream) {
   TAGREC_REQUIRE(Nn && X && dP1 && dP2 && dW1p && dW2p && workspace, "ngcf_wgrad: null pointer");
+  TAGREC_REQUIRE(n_rows >= 0, "ngcf_wgrad: bad shape");
   TAGREC_REQUIRE(workspace_floats >= tagrec_ngcf_wgrad_workspace(Din, Dout), "ngcf_wgrad: workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
 #define CALL(A, B) launch_wgrad<A, B>(Nn, X, dP1, dP2, n_rows, dW1p, dW2p, workspace, row_mask, s)

@@ -381,16 +381,27 @@ __global__ __launch_bounds__(kThreads) void bpr_bwd_kernel(const float* __restri
   const float g1 = g ? g[1] : 1.f;
   const int64_t u = trip[3 * b], p = trip[3 * b + 1], n = trip[3 * b + 2];
   const float c = g0 * coef[b] * inv_b;
+  const float cr = g1 * reg * inv_b;
+  const bool reg_on = Ur && cr != 0.f;
+  // L2 part on the main tables into the main gradient buffers (the models that regularise the propagated rows): ONE addition
+  // per element and slot.  Two separate additions per slot made a row that two triplets name the sum of four atomics from two
+  // waves, whose interleaving -- and so the rounding -- changed from run to run; a sum of two is the same in either order.
+  const bool fused = dU && reg_on && dUr == dU && dIr == dI && Ur == U && Ir == I && ldr == ld && Dr == D;
   if (dU) {
     for (int k = lane; k < D; k += kWave) {
       const float uv = U[u * ld + k], pv = I[p * ld + k], nv = I[n * ld + k];
-      atomicAdd(&dU[u * ld + k], c * (nv - pv));
-      atomicAdd(&dI[p * ld + k], -c * uv);
-      atomicAdd(&dI[n * ld + k], c * uv);
+      float du = c * (nv - pv), dp = -c * uv, dn = c * uv;
+      if (fused) {
+        du = fmaf(cr, uv, du);
+        dp = fmaf(cr, pv, dp);
+        dn = fmaf(cr, nv, dn);
+      }
+      atomicAdd(&dU[u * ld + k], du);
+      atomicAdd(&dI[p * ld + k], dp);
+      atomicAdd(&dI[n * ld + k], dn);
     }
   }
-  const float cr = g1 * reg * inv_b;
-  if (Ur && cr != 0.f) {
+  if (reg_on && !fused) {
     for (int k = lane; k < Dr; k += kWave) {
       atomicAdd(&dUr[u * ldr + k], cr * Ur[u * ldr + k]);
       atomicAdd(&dIr[p * ldr + k], cr * Ir[p * ldr + k]);

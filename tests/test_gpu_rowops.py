@@ -322,6 +322,35 @@ def test_bpr_reg_modes_and_upstream_gradients(D, B, mode, g):
     chk.done()
 
 
+def test_bpr_same_buffers_one_addition_per_slot():
+    """mode 'same' (the L2 part on the main tables, into the main gradient buffers: the models that regularise the propagated
+    rows): a slot adds its main and its L2 term as ONE value, so a row that two triplets name is a sum of two atomics -- the
+    same bits in either order.  Every user is named by triplets b and b + 128 (different blocks), every item as the positive
+    of one triplet and the negative of another; 25 runs must agree bit for bit, and the first is held to the fp64 gradients."""
+    chk = Chk("bpr same buffers, rows named twice")
+    B, nu, ni, D = 256, 128, 256, 64
+    W = _slots(nu + ni, D, 8, seed=5)
+    U, I = W[:nu, :D], W[nu:, :D]
+    b = torch.arange(B)
+    trip = torch.stack([b % nu, b, (b + 37) % ni], 1)
+    tg = trip.to(DEV)
+    res, coef = rowops.bpr_fwd(U, I, U, I, tg, _lib.LOSS_SOFTPLUS)
+    g = [0.37, -2.0]
+    gg = torch.tensor(g, dtype=torch.float32, device=DEV)
+    runs = []
+    for _ in range(25):
+        dW = _grad_slots(W, D)
+        rowops.bpr_bwd(U, I, U, I, tg, coef, gg, dW[:nu, :D], dW[nu:, :D], dW[:nu, :D], dW[nu:, :D])
+        runs.append(dW)
+    ref = _bpr_bwd_ref(U, I, U, I, trip, coef, g)
+    for k, kr, got in (("U", "Ur", runs[0][:nu, :D]), ("I", "Ir", runs[0][nu:, :D])):
+        s, m, mult = (ref[k][i] + ref[kr][i] for i in range(3))
+        assert (mult == 4).all()                                     # two slots, a main and an L2 term each
+        chk.close("d" + k, got, s, m, C_BPR[k] + mult)
+    assert all(_same_bits(runs[0][:, :D], r[:, :D]) for r in runs[1:]), "a row named by two triplets changed from run to run"
+    chk.done()
+
+
 # the issue's gaps, and two between 10 and 20 where softplus still differs from x by more than fp32 resolves
 GAPS = (-100.0, -20.5, -1e-4, 0.0, 10.5, 15.0, 19.99, 20.0, 20.01, 100.0)
 

@@ -487,6 +487,23 @@ int tagrec_catsoftmax_masked_bwd_f32(const float* Q, int64_t ldq, const int64_t*
                                      float* dQ, float* dQreg, float* dTreg, void* stream, const int64_t* mask_ptr,
                                      const int32_t* mask_cols);
 
+/* ---- K22: nearest-centroid assignment, the E-step of k-means; the n x K distances are never stored (csrc/kmeans.hip) ----
+ * X [n, D] (row stride ldx floats): the rows to assign.  C [K, D] (stride ldc): the centroids.  The tile scheme is the pair
+ * kernels' (csrc/pairtile.h): a block owns 64 rows of X and walks every 64-row tile of C; there is no column split, so a call
+ * with few rows and very many centroids walks serially.
+ *   h_j    = 0.5 |c_j|^2                           (one fmaf chain over ascending d, then * 0.5f: the same expression for
+ *                                                   every column, written to half_norm [K] -- scratch the caller provides)
+ *   s_ij   = x_i . c_j - h_j                       (exact-fp32 MFMA 16x16x4, ascending feature blocks; one subtraction)
+ *   assign[i] = argmax_j s_ij                      = the Euclidean nearest centroid; TIES GO TO THE LOWER ID
+ *   best[i]   = s_{i, assign_i}                    (NULL: not written); the inertia is sum_i |x_i|^2 - 2 best_i
+ * Two identical rows of C score bit-identically, so the lower of their ids wins every row.  A column past K is never admitted
+ * (it would score 0), padded feature columns add exact zeros.  No atomics, nothing allocated: the outputs are a pure function
+ * of the operands.  D must be a multiple of 4 in 8 .. 256, n >= 1 and 1 <= K <= 2^31 - 1: anything else is
+ * TAGREC_E_UNSUPPORTED.  Rows that are 16-byte aligned with a stride that is a multiple of 4 are staged by float4 loads, any
+ * other by scalar loads.  NaN / Inf operands give an unspecified assignment inside [0, K); no read leaves the operands. */
+int tagrec_kmeans_assign_f32(const float* X, int64_t ldx, int64_t n, const float* C, int64_t ldc, int64_t K, int D,
+                             float* half_norm, int64_t* assign, float* best, void* stream);
+
 /* ---- DirectAU on COMPACT rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
  * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub; repeated rows are kept.
  * Ureg / Ireg [B, Dreg] (stride ldreg): the rows the L2 term reads (both NULL: no L2 term).  x^ = x / max(|x|, 1e-12).

@@ -12,6 +12,8 @@ Reference name                      here
   model.DisenHAN                      tagrec_amd.DisenHAN (disenhan_config(**kw))
   -- (not in the reference)           tagrec_amd.SimGCL: LightGCN + contrastive noise views (get_config("simgcl"))
   -- (not in the reference)           tagrec_amd.DirectAU: LightGCN under the alignment / uniformity loss (get_config("directau"))
+  -- (not in the reference)           tagrec_amd.NCL: LightGCN + structure / prototype contrast (get_config("ncl"))
+  -- (not in the reference)           tagrec_amd.kmeans: Lloyd's algorithm on the device (kmeans.py)
   train_data.BPR_training_data        tagrec_amd.BPR_training_data
   training.Basic_train / Basic_test   tagrec_amd.Basic_train / Basic_test
   training.utils.user_group_split     tagrec_amd.user_group_split
@@ -27,6 +29,8 @@ from .graph import Graph, creat_adj  # noqa: F401
 from .lightgcn import LightGCN  # noqa: F401
 from .simgcl import SimGCL  # noqa: F401
 from .directau import DirectAU  # noqa: F401
+from .kmeans import kmeans  # noqa: F401
+from .ncl import NCL  # noqa: F401
 from .ngcf import NGCF  # noqa: F401
 from .tgcn import TGCN  # noqa: F401
 from .dgcf import DGCF  # noqa: F401

@@ -68,6 +68,13 @@ _PER_MODEL = {
     # (directau.py, rowops.directau_*); batches are [B, 2], nothing is sampled
     "directau": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100,
                  "au_gamma": 1.0, "au_t": 2.0, "use_tag": False, "pair_batches": True},
+    # NCL (not in the reference; Lin et al., WWW 2022): LightGCN plus a structure contrast (a node against its two-hop view)
+    # and a prototype contrast (a node against the k-means centroid of its cluster, re-clustered every epoch from
+    # ncl_warm_up on) (ncl.py, kmeans.py, rowops.kmeans_assign / catsoftmax_*).  The terms are MEANS over the batch; the
+    # defaults are untuned and no accuracy run exists
+    "ncl": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100, "use_tag": False,
+            "ncl_struct_rate": 5e-4, "ncl_proto_rate": 3e-4, "ncl_alpha": 1.0, "ncl_temperature": 0.1,
+            "ncl_clusters": 1000, "ncl_kmeans_iters": 20, "ncl_warm_up": 20},
 }
 MAX_AU_T = 20.0                   # a term of the uniformity sum is >= e^(-4 au_t): e^-80 is still a normal fp32 number
 
@@ -89,6 +96,8 @@ def get_config(model="lightgcn", **overrides):
         check_contrastive(cfg)
     if model == "directau":
         check_alignment(cfg)
+    if model == "ncl":
+        check_ncl(cfg)
     return cfg
 
 
@@ -192,6 +201,29 @@ def check_alignment(cfg):
     if isinstance(t, bool) or not isinstance(t, (int, float)) or not 0 < t <= MAX_AU_T:
         raise TagrecError(f"au_t must be a number in (0, {MAX_AU_T:g}], got {t!r}")
     return float(gamma), float(t)
+
+
+def check_ncl(cfg):
+    """The seven NCL keys of a config -> (struct_rate, proto_rate, alpha, temperature, clusters, kmeans_iters, warm_up); a bad
+    value is refused: the rates and alpha finite and >= 0, the temperature finite and > 0, clusters and iterations integers
+    >= 1, warm-up an integer >= 0."""
+    from ._lib import TagrecError
+    d = _PER_MODEL["ncl"]
+    vals = {k: cfg.get(k, d[k]) for k in ("ncl_struct_rate", "ncl_proto_rate", "ncl_alpha", "ncl_temperature", "ncl_clusters",
+                                          "ncl_kmeans_iters", "ncl_warm_up")}
+    for name in ("ncl_struct_rate", "ncl_proto_rate", "ncl_alpha"):
+        v = vals[name]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf"):
+            raise TagrecError(f"{name} must be a finite number >= 0, got {v!r}")
+    tau = vals["ncl_temperature"]
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < float("inf"):
+        raise TagrecError(f"ncl_temperature must be a finite number > 0, got {tau!r}")
+    for name, low in (("ncl_clusters", 1), ("ncl_kmeans_iters", 1), ("ncl_warm_up", 0)):
+        v = vals[name]
+        if isinstance(v, bool) or not isinstance(v, int) or v < low:
+            raise TagrecError(f"{name} must be an integer >= {low}, got {v!r}")
+    return (float(vals["ncl_struct_rate"]), float(vals["ncl_proto_rate"]), float(vals["ncl_alpha"]), float(tau),
+            vals["ncl_clusters"], vals["ncl_kmeans_iters"], vals["ncl_warm_up"])
 
 
 CFG =get_config("lightgcn")

@@ -7,6 +7,7 @@ argument meaning, backed by the HIP library through `torch.autograd.Function`s.
     l2reg_loss(*embs)                        loss.py:27-32
     transtag_loss / transe_loss              loss.py:35-50
     cor_loss(factor_emb, factor_k)           loss.py:53-80   (kernels: csrc/cor.hip, host side: cor.py)
+    ncl_structure_loss / ncl_prototype_loss  --              (NCL's two contrast terms on the catalogue-softmax kernels; model: ncl.py)
     creat_adj(...)                           adj.py:38-46   (re-exported from graph.py)
 
 Inputs must be GPU tensors; there is no CPU path.
@@ -328,6 +329,99 @@ def catalogue_softmax_loss(U, I, Ureg, Ireg, pairs, temperature=1.0, plans=None,
     or not it is listed."""
     out = stage_loss(S.Catalogue(float(temperature), positives), U, I, Ureg, Ireg, pairs, plans)
     return out[0], out[1]
+
+
+class _NodeContrast(torch.autograd.Function):
+    """One softmax of the NCL terms: the mean over b of logsumexp_n(z_bn) - z_{b, target_b}, z_bn = nrm(Y[qrows_b]) . t_n /
+    temperature, through the catalogue-softmax kernels (`rowops.catsoftmax_*`, no L2 rows).  Repeated qrows are kept.
+      t_const False   T = raw rows, t_n = nrm(T[n]); the gradient flows into BOTH operands: dQ -> rownorm_bwd -> a fold of
+                      the repeated rows into dY; the dense dT -> rownorm_bwd -> dT.
+      t_const True    T = unit rows taken as they are (a centroid table), a constant: only dY is returned; the dT the backward
+                      kernel stores all the same lands in a scratch buffer and is dropped.
+    plan: the `rowops.row_list_plan` of qrows over the rows of Y (the fold then runs in a fixed order), or None."""
+
+    @staticmethod
+    def forward(ctx, Y, T, qrows, target, temperature, t_const, plan):
+        what = "ncl contrast"
+        for t, nm in ((Y, "Y"), (T, "T")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+                raise _lib.TagrecError(f"{what}: {nm} must be a 2-d float32 GPU tensor")
+        qrows = _lib.require_gpu_tensor(qrows, torch.int64, f"{what} qrows")
+        target = _lib.require_gpu_tensor(target, torch.int64, f"{what} target")
+        q_raw = Y.index_select(0, qrows)
+        Q, inv_q = rowops.rownorm_fwd(q_raw)
+        if t_const:
+            t_raw, inv_t, Tn = None, None, T.contiguous()
+        else:
+            t_raw = T.contiguous()
+            Tn, inv_t = rowops.rownorm_fwd(t_raw)
+        res, lse, _ = rowops.catsoftmax_fwd(Q, Tn, target, temperature)
+        ctx.saved = (q_raw, Q, inv_q, t_raw, Tn, inv_t, qrows, target, lse)
+        ctx.tau, ctx.plan, ctx.y_shape = float(temperature), plan, Y.shape
+        return res[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        q_raw, Q, inv_q, t_raw, Tn, inv_t, qrows, target, lse = ctx.saved
+        ctx.saved = None
+        g2 = torch.zeros(2, dtype=torch.float32, device=Q.device)
+        g2[0] = g
+        dT = torch.empty_like(Tn)                  # t_const: scratch, dropped
+        dQ = rowops.catsoftmax_bwd(Q, Tn, target, ctx.tau, lse, g2, dT)
+        dq_raw = rowops.rownorm_bwd(q_raw, inv_q, dQ, 1.0, torch.empty_like(q_raw))
+        dY = rowops.fold_rows(torch.zeros(ctx.y_shape, dtype=torch.float32, device=Q.device), qrows, dq_raw, ctx.plan)
+        dT_raw = None if t_raw is None else rowops.rownorm_bwd(t_raw, inv_t, dT, 1.0, torch.empty_like(t_raw))
+        return dY, dT_raw, None, None, None, None, None
+
+
+def _ncl_batch(what, batch):
+    """(u_b, i_b): a batch's first two columns, each contiguous."""
+    if batch.dim() != 2 or batch.shape[1] < 2 or batch.shape[0] < 1:
+        raise _lib.TagrecError(f"{what}: a batch of shape {tuple(batch.shape)} has no (user, item) columns")
+    return batch[:, 0].contiguous(), batch[:, 1].contiguous()
+
+
+def ncl_structure_loss(x0, norm_adj, n_user, n_item, batch, temperature, alpha=1.0, deterministic=False):
+    """NCL's structure term (Lin et al., WWW 2022, hyper_layers = 1) as a MEAN over the batch (the paper's code sums):
+    y2 = A (A x0) is the raw two-hop product (two `split_mm`), (u_b, i_b) the batch's columns 0 and 1, repeats kept;
+        L_su = mean_b [logsumexp_n(nrm(y2[u_b]) . nrm(U0[n]) / t) - nrm(y2[u_b]) . nrm(U0[u_b]) / t],   U0 = x0[:n_user]
+        L_si   likewise with y2[n_user + i_b], I0 = x0[n_user : n_user + n_item] and i_b
+    -> L_su + alpha * L_si.  The gradient flows into x0 through both operands of each softmax.  deterministic: the repeated
+    rows' gradients are folded in a fixed order (`rowops.row_list_plan`), the same bits on every run."""
+    what = "ncl_structure_loss"
+    batch = _lib.require_gpu_tensor(batch.contiguous(), torch.int64, f"{what} batch")
+    ub, ib = _ncl_batch(what, batch)
+    n, D = x0.shape
+    y2 = split_mm(norm_adj, split_mm(norm_adj, x0))
+    qi = ib + n_user
+    pu = rowops.row_list_plan(ub, n, None, D) if deterministic else None
+    pi = rowops.row_list_plan(qi, n, None, D) if deterministic else None
+    l_u = _NodeContrast.apply(y2, x0[:n_user], ub, ub, temperature, False, pu)
+    l_i = _NodeContrast.apply(y2, x0[n_user:n_user + n_item], qi, ib, temperature, False, pi)
+    return l_u + alpha * l_i
+
+
+def ncl_prototype_loss(x0, n_user, n_item, batch, cent_u, cent_i, cluster_u, cluster_i, temperature, alpha=1.0,
+                       deterministic=False):
+    """NCL's prototype term as a MEAN over the batch: a node's ego row against the centroid table of its side,
+        L_pu = mean_b [logsumexp_k(nrm(U0[u_b]) . Cu[k] / t) - nrm(U0[u_b]) . Cu[cluster_u[u_b]] / t]      and L_pi likewise
+    -> L_pu + alpha * L_pi.  cent_u / cent_i [K, D]: the ROW-NORMALISED centroids; cluster_u [n_user] / cluster_i [n_item]:
+    int64 cluster ids.  All four are constants: the gradient flows into x0 through the batch rows only."""
+    what = "ncl_prototype_loss"
+    batch = _lib.require_gpu_tensor(batch.contiguous(), torch.int64, f"{what} batch")
+    ub, ib = _ncl_batch(what, batch)
+    n, D = x0.shape
+    for nm, c, cl, cnt in (("user", cent_u, cluster_u, n_user), ("item", cent_i, cluster_i, n_item)):
+        if c.dim() != 2 or c.shape[1] != D or c.dtype != torch.float32 or not c.is_cuda:
+            raise _lib.TagrecError(f"{what}: the {nm} centroids must be a float32 GPU tensor [K, {D}], got {tuple(c.shape)}")
+        if cl.shape != (cnt,) or cl.dtype != torch.int64 or not cl.is_cuda:
+            raise _lib.TagrecError(f"{what}: the {nm} cluster ids must be an int64 GPU tensor [{cnt}]")
+    qi = ib + n_user
+    pu = rowops.row_list_plan(ub, n, None, D) if deterministic else None
+    pi = rowops.row_list_plan(qi, n, None, D) if deterministic else None
+    l_u = _NodeContrast.apply(x0, cent_u.detach(), ub, cluster_u.index_select(0, ub), temperature, True, pu)
+    l_i = _NodeContrast.apply(x0, cent_i.detach(), qi, cluster_i.index_select(0, ib), temperature, True, pi)
+    return l_u + alpha * l_i
 
 
 class AuRoute(NamedTuple):

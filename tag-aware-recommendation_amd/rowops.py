@@ -449,6 +449,52 @@ def catsoftmax_bwd(Q, T, target, temperature, lse, g, dT, dQ=None, qrow=None, Qr
     return dQ
 
 
+# ---- nearest-centroid assignment: the fused n x K search of k-means (csrc/kmeans.hip) ----
+
+def _kmeans_args(what, X, C, assign, best):
+    """(n, K, D, assign, best) of an assignment call after the checks that need no host read."""
+    for nm, t in (("X", X), ("C", C)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise _lib.TagrecError(f"{what}: {nm} must be a 2-d float32 GPU tensor")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise _lib.TagrecError(f"{what}: {nm} must have unit inner stride, got {t.stride(1)}")
+    if X.shape[1] != C.shape[1] or X.device != C.device:
+        raise _lib.TagrecError(f"{what}: X {tuple(X.shape)} and C {tuple(C.shape)} must be of one width and on one device")
+    n, K, D = X.shape[0], C.shape[0], X.shape[1]
+    if n < 1:
+        raise _lib.TagrecError(f"{what}: no rows to assign (n = 0)")
+    if K < 1:
+        raise _lib.TagrecError(f"{what}: an empty centroid table (K = 0) has no nearest row")
+    if D < 8 or D > 256 or D % 4 != 0:
+        raise _lib.TagrecError(f"{what}: the width must be a multiple of 4 in 8 .. 256, got {D}")
+    if assign is None:
+        assign = torch.empty(n, dtype=torch.int64, device=X.device)
+    elif not isinstance(assign, torch.Tensor) or assign.dtype != torch.int64 or assign.shape != (n,) or not assign.is_contiguous() \
+            or assign.device != X.device:
+        raise _lib.TagrecError(f"{what}: assign must be a contiguous int64 tensor of shape [{n}] on {X.device}")
+    if best is None:
+        best = torch.empty(n, dtype=torch.float32, device=X.device)
+    elif not isinstance(best, torch.Tensor) or best.dtype != torch.float32 or best.shape != (n,) or not best.is_contiguous() \
+            or best.device != X.device:
+        raise _lib.TagrecError(f"{what}: best must be a contiguous float32 tensor of shape [{n}] on {X.device}")
+    return n, K, D, assign, best
+
+
+def kmeans_assign(X, C, assign=None, best=None, half_norm=None):
+    """The nearest row of C [K, D] for every row of X [n, D] (both may be strided row views): s_ij = x_i . c_j - 0.5 |c_j|^2,
+    assign[i] = argmax_j s_ij -- the Euclidean nearest centroid, ties to the LOWER id -- and best[i] = the winning score
+    (the inertia is sum_i |x_i|^2 - 2 best_i).  -> (assign int64 [n], best float32 [n]); both are allocated when None.
+    The n x K scores are never stored.  half_norm: float32 [K] scratch for the centroids' half norms (None: allocated)."""
+    what = "kmeans_assign"
+    n, K, D, assign, best = _kmeans_args(what, X, C, assign, best)
+    if half_norm is None:
+        half_norm = torch.empty(K, dtype=torch.float32, device=X.device)
+    elif half_norm.dtype != torch.float32 or half_norm.numel() < K or not half_norm.is_contiguous() or half_norm.device != X.device:
+        raise _lib.TagrecError(f"{what}: half_norm must be a contiguous float32 tensor of >= {K} elements on {X.device}")
+    check(load().tagrec_kmeans_assign_f32(X, _row_ld(X), n, C, _row_ld(C), K, D, half_norm, assign, best, stream_ptr()), what)
+    return assign, best
+
+
 # ---- DirectAU on compact rows: alignment + uniformity on the unit sphere, fused B x B kernels (csrc/directau.hip) ----
 
 AU_PREP_ROWS = 4         # batch positions per block of the prep kernel: `partials` holds two floats per block of it ...

@@ -323,6 +323,8 @@ class Basic_train:
         history = []
         for ep in range(self.cfg["epochs"]):
             model.train()
+            if hasattr(model, "begin_epoch"):      # per-epoch work outside the steps (NCL re-clusters its node tables)
+                model.begin_epoch(ep)
             for i in range(self.train_sphase):
                 start = time.time()
                 loss_list = epoch_training(self.train_data[i], self.loss_func[i], self.opt[i], verbose=verbose, graphs=self.graphs)

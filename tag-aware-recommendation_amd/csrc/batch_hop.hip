@@ -538,8 +538,7 @@ extern "C" int tagrec_batch_hop_plan(const tagrec_graph* gt, const int64_t* rows
   TAGREC_REQUIRE(gt != nullptr && rows != nullptr && ws != nullptr && err != nullptr, "batch_hop_plan: null pointer");
   // gt = the TRANSPOSE of the matrix the hop multiplies by: its row b lists the destinations of source b
   const int64_t n_dst = gt->n_cols;
-  int rc = check_shape("batch_hop_plan", n_dst, n_listed, capacity);
-  if (rc != TAGREC_OK) return rc;
+  TAGREC_TRY(check_shape("batch_hop_plan", n_dst, n_listed, capacity));
   TAGREC_REQUIRE(gt->n_rows == n_dst, "batch_hop_plan: square matrix expected");   // (a leader may be a destination itself)
   TAGREC_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 255u) == 0, "batch_hop_plan: the workspace must be 256-byte aligned");
   HopLayout L;
@@ -556,7 +555,7 @@ extern "C" int tagrec_batch_hop_plan(const tagrec_graph* gt, const int64_t* rows
   int32_t* dst = reinterpret_cast<int32_t*>(base + L.dst);
   int32_t* src = reinterpret_cast<int32_t*>(base + L.src);
   float* w = reinterpret_cast<float*>(base + L.w);
-  const GraphView gv{gt->n_rows, gt->rowptr, gt->col, gt->val, gt->n_cols};
+  const GraphView gv = view_of(gt);
   const int32_t cap = static_cast<int32_t>(capacity);
   const int nb = static_cast<int>(L.n_buckets);
   const size_t walk_lds = static_cast<size_t>(nb) * sizeof(int32_t);
@@ -588,15 +587,8 @@ extern "C" int64_t tagrec_batch_hop_list_result(int64_t n_rows, int64_t n_listed
 }
 
 extern "C" int tagrec_batch_hop_grid_rows(int D) {
-  switch (D) {
-    case 8: return hop_grid_rows<2>();
-    case 16: return hop_grid_rows<4>();
-    case 32: return hop_grid_rows<8>();
-    case 64: return hop_grid_rows<16>();
-    case 128: return hop_grid_rows<32>();
-    case 256: return hop_grid_rows<64>();
-    default: return 0;
-  }
+  if (!is_vec_width(D)) return 0;
+  return vec_width_dispatch(D, "batch_hop_grid_rows", [](auto lc) { return hop_grid_rows<decltype(lc)::value>(); });
 }
 
 extern "C" int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* ws, int64_t ws_bytes, int64_t n_listed, int64_t capacity,
@@ -608,8 +600,7 @@ extern "C" int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* w
   TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, "batch_hop_normbwd: null X_raw, inv_norm or dZ");
   TAGREC_REQUIRE(static_cast<const void*>(G_in) != static_cast<const void*>(G_out), "batch_hop_normbwd: output aliases the gathered input");
   TAGREC_REQUIRE(aligned16(G_in) && aligned16(G_out) && aligned16(X_raw) && aligned16(dZ), "batch_hop_normbwd: rows must be 16-byte aligned");
-  int rc = check_shape("batch_hop_normbwd", g->n_rows, n_listed, capacity);
-  if (rc != TAGREC_OK) return rc;
+  TAGREC_TRY(check_shape("batch_hop_normbwd", g->n_rows, n_listed, capacity));
   HopLayout L;
   hop_layout(g->n_rows, n_listed, capacity, &L);
   TAGREC_REQUIRE(ws_bytes >= static_cast<int64_t>(L.total), "batch_hop_normbwd: workspace smaller than tagrec_batch_hop_workspace(...)");
@@ -619,13 +610,5 @@ extern "C" int tagrec_batch_hop_normbwd_f32(const tagrec_graph* g, const void* w
                    static_cast<int32_t>(L.dest_cap)};
   const HopEpi e{G_out, inv_norm, X_raw, dZ, d_scale, DropMask{0.f, 0}, out_flags, row_mask, dz_flags};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (D) {
-    case 8: return launch_hop<2>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    case 16: return launch_hop<4>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    case 32: return launch_hop<8>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    case 64: return launch_hop<16>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    case 128: return launch_hop<32>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    case 256: return launch_hop<64>(g->n_rows, g->rowptr, pl, G_in, e, s);
-    default: return fail(TAGREC_E_UNSUPPORTED, "batch_hop_normbwd: D must be 8 .. 256, a power of two");
-  }
+  return vec_width_dispatch(D, "batch_hop_normbwd", [&](auto lc) { return launch_hop<decltype(lc)::value>(g->n_rows, g->rowptr, pl, G_in, e, s); });
 }

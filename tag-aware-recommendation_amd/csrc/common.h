@@ -27,6 +27,13 @@ inline int fail(int code, const std::string& msg) {
     if (!(cond)) return ::tagrec::fail(TAGREC_E_INVALID, std::string(msg)); \
   } while (0)
 
+// hand a callee's refusal on as it is (its message is already in the error slot)
+#define TAGREC_TRY(expr)              \
+  do {                                \
+    const int _rc = (expr);           \
+    if (_rc != TAGREC_OK) return _rc; \
+  } while (0)
+
 #define TAGREC_LAUNCH_CHECK() TAGREC_HIP(hipGetLastError())
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

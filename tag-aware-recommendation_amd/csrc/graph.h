@@ -1,6 +1,8 @@
-// The CSR handle behind `tagrec_graph*` and the device-side views of it, shared by the kernels that walk
-// adjacency rows (spmm.hip, routing.hip).
+// The CSR handle behind `tagrec_graph*`, the device-side views of it and the host-side launch helpers, shared by the
+// kernels that walk adjacency rows (spmm.hip, routing.hip, batch_hop.hip).
 #pragma once
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -51,5 +53,54 @@ int ensure_slab(const tagrec_graph* g, int width);
 
 // *count = number of non-zero bytes of flags[0..n) (rowops.hip)
 int count_flags(const uint8_t* flags, int64_t n, unsigned* count, hipStream_t s);
+
+// ---- host side: what every launch over a handle starts from ---------------------------------------------------------
+inline GraphView view_of(const tagrec_graph* g) { return GraphView{g->n_rows, g->rowptr, g->col, g->val, g->n_cols}; }
+
+// blocks of a grid that gives each of n rows one of the `per_block` slots of a block (default: one wavefront per row)
+inline unsigned row_blocks(int64_t n, int per_block = kWavesPerBlock) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
+
+// The long-row part of a launch whose rows are `width` floats wide: empty when the graph has no long row.
+inline int long_view(const tagrec_graph* g, int width, LongView* lv) {
+  *lv = LongView{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
+  if (g->n_long > 0) {
+    TAGREC_TRY(ensure_slab(g, width));
+    lv->slab = g->slab;
+    lv->chunk_blocks = row_blocks(g->n_chunks);
+  }
+  return TAGREC_OK;
+}
+
+// A row-walking launch and the fold of its long rows: main_launch(lv) puts lv.chunk_blocks blocks in front of its own
+// grid, finish_launch() folds the slab into the g->n_long long rows and runs only when there are any.
+template <typename Main, typename Finish>
+int launch_with_long_rows(const tagrec_graph* g, int width, Main&& main_launch, Finish&& finish_launch) {
+  LongView lv;
+  TAGREC_TRY(long_view(g, width, &lv));
+  main_launch(lv);
+  TAGREC_LAUNCH_CHECK();
+  if (g->n_long > 0) {
+    finish_launch();
+    TAGREC_LAUNCH_CHECK();
+  }
+  return TAGREC_OK;
+}
+
+// The vector kernels cover rows of D = 8 .. 256 floats, a power of two: LPR = D / 4 lanes hold one row as float4s.
+inline bool is_vec_width(int D) { return D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256; }
+
+// Dispatch on D to a functor templated on LPR.
+template <typename F>
+int vec_width_dispatch(int D, const char* who, F&& f) {
+  switch (D) {
+    case 8: return f(std::integral_constant<int, 2>{});
+    case 16: return f(std::integral_constant<int, 4>{});
+    case 32: return f(std::integral_constant<int, 8>{});
+    case 64: return f(std::integral_constant<int, 16>{});
+    case 128: return f(std::integral_constant<int, 32>{});
+    case 256: return f(std::integral_constant<int, 64>{});
+    default: return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": D must be 8 .. 256, a power of two");
+  }
+}
 
 }  // namespace tagrec

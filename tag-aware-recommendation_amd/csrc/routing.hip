@@ -466,18 +466,6 @@ int k_dispatch(int K, const char* who, F&& f) {
   }
 }
 
-int long_view(const tagrec_graph* g, int width, LongView* lv) {
-  TAGREC_REQUIRE(!g->deferred, "routing kernels need a handle created with a host read (tagrec_graph_create / _ws)");
-  *lv = LongView{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
-  if (g->n_long > 0) {
-    int rc = ensure_slab(g, width);
-    if (rc != TAGREC_OK) return rc;
-    lv->slab = g->slab;
-    lv->chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-  }
-  return TAGREC_OK;
-}
-
 }  // namespace
 
 extern "C" int tagrec_route_softmax_f32(const float* logits, float* w, int64_t nnz, int K, void* stream) {
@@ -500,20 +488,17 @@ extern "C" int tagrec_route_rowsum_rsqrt_f32(const tagrec_graph* g, const float*
   hipStream_t s = static_cast<hipStream_t>(stream);
   return k_dispatch(K, "route_rowsum_rsqrt", [&](auto kc) {
     constexpr int KK = decltype(kc)::value;
-    LongView lv;
-    int rc = long_view(g, KK, &lv);
-    if (rc != TAGREC_OK) return rc;
-    const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-    const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-    route_rowsum_kernel<KK><<<blocks + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(gv, w, d, lv);
-    TAGREC_LAUNCH_CHECK();
-    if (g->n_long > 0) {
-      const int64_t n = g->n_long * KK;
-      route_rowsum_finish_kernel<KK><<<static_cast<unsigned>((n + 255) / 256), 256, 0, s>>>(gv, g->long_rows, g->long_base,
-                                                                                            g->n_long, g->slab, d);
-      TAGREC_LAUNCH_CHECK();
-    }
-    return TAGREC_OK;
+    TAGREC_REQUIRE(!g->deferred, "routing kernels need a handle created with a host read (tagrec_graph_create / _ws)");
+    const GraphView gv = view_of(g);
+    return launch_with_long_rows(
+        g, KK,
+        [&](const LongView& lv) {
+          route_rowsum_kernel<KK><<<row_blocks(g->n_rows) + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(gv, w, d, lv);
+        },
+        [&] {
+          route_rowsum_finish_kernel<KK><<<row_blocks(g->n_long * KK, 256), 256, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long,
+                                                                                         g->slab, d);
+        });
   });
 }
 
@@ -551,19 +536,17 @@ extern "C" int tagrec_route_spmm_ex_f32(const tagrec_graph* g, const float* W, i
   const RouteEpi e{Y, Yn, inv, post, self, B, b_scale, row_mask, in_flags, in_count};
   return route_dispatch(D, K, "route_spmm", [&](auto lc, auto kc) {
     constexpr int LPR = decltype(lc)::value, KK = decltype(kc)::value;
-    LongView lv;
-    int rc = long_view(g, LPR * 4, &lv);
-    if (rc != TAGREC_OK) return rc;
-    const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-    const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-    route_spmm_kernel<LPR, KK><<<blocks + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(gv, W, X, e, lv);
-    TAGREC_LAUNCH_CHECK();
-    if (g->n_long > 0) {
-      const unsigned fb = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-      route_spmm_finish_kernel<LPR, KK><<<fb, kWavesPerBlock * kWave, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-      TAGREC_LAUNCH_CHECK();
-    }
-    return TAGREC_OK;
+    TAGREC_REQUIRE(!g->deferred, "routing kernels need a handle created with a host read (tagrec_graph_create / _ws)");
+    const GraphView gv = view_of(g);
+    return launch_with_long_rows(
+        g, LPR * 4,
+        [&](const LongView& lv) {
+          route_spmm_kernel<LPR, KK><<<row_blocks(g->n_rows) + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(gv, W, X, e, lv);
+        },
+        [&] {
+          route_spmm_finish_kernel<LPR, KK><<<row_blocks(g->n_long), kWavesPerBlock * kWave, 0, s>>>(gv, g->long_rows, g->long_base,
+                                                                                                    g->n_long, g->slab, e);
+        });
   });
 }
 
@@ -582,11 +565,9 @@ extern "C" int tagrec_route_score_rows_f32(const tagrec_graph* g, const float* H
   hipStream_t s = static_cast<hipStream_t>(stream);
   return route_dispatch(D, K, "route_score", [&](auto lc, auto kc) {
     constexpr int LPR = decltype(lc)::value, KK = decltype(kc)::value;
-    LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr,
-                g->n_long > 0 ? static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock) : 0u};
-    const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-    const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-    route_score_kernel<LPR, KK><<<blocks + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(gv, H, T, logits, accumulate, lv, row_mask);
+    const LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, g->n_long > 0 ? row_blocks(g->n_chunks) : 0u};   // no slab: no fold
+    route_score_kernel<LPR, KK><<<row_blocks(g->n_rows) + lv.chunk_blocks, kWavesPerBlock * kWave, 0, s>>>(view_of(g), H, T, logits,
+                                                                                                          accumulate, lv, row_mask);
     TAGREC_LAUNCH_CHECK();
     return TAGREC_OK;
   });
@@ -632,9 +613,7 @@ extern "C" int tagrec_row_softmax_fwd_f32(const tagrec_graph* g, const float* lo
   TAGREC_REQUIRE(g, "row_softmax_fwd: null graph");
   TAGREC_REQUIRE(g->nnz == 0 || (logits && a), "row_softmax_fwd: null pointer");
   if (g->n_rows == 0 || g->nnz == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  row_softmax_fwd_kernel<<<blocks, kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(gv, logits, a);
+  row_softmax_fwd_kernel<<<row_blocks(g->n_rows), kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(view_of(g), logits, a);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }
@@ -643,9 +622,7 @@ extern "C" int tagrec_row_softmax_bwd_f32(const tagrec_graph* g, const float* a,
   TAGREC_REQUIRE(g, "row_softmax_bwd: null graph");
   TAGREC_REQUIRE(g->nnz == 0 || (a && da && dlogits), "row_softmax_bwd: null pointer");
   if (g->n_rows == 0 || g->nnz == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  row_softmax_bwd_kernel<<<blocks, kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(gv, a, da, dlogits);
+  row_softmax_bwd_kernel<<<row_blocks(g->n_rows), kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(view_of(g), a, da, dlogits);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }

@@ -30,31 +30,31 @@ constexpr int kMaxGenericBlocks = 8;  // scalar kernel keeps D <= 512 in registe
 enum Epi { EPI_NONE = 0, EPI_NORM_ACC = 1, EPI_NORMBWD = 2, EPI_AXPY = 3, EPI_SS = 4, EPI_NORMBWD_DOT = 5 };
 
 struct EpiArgs {
-  float* Y;               // [n_rows, D] product (or gradient) out
-  float* inv_norm;        // NORM_ACC: out; NORMBWD / NORMBWD_DOT: in; SS: out = this shard's sum of squares per row
-  float* accum;           // NORM_ACC: accum += s * normalize(y)
-  const float* Xraw;      // NORMBWD
-  const float* B;         // NORMBWD / NORMBWD_DOT: dZ ; AXPY: B
-  const float* dot;       // NORMBWD_DOT: z . (s dZ) per row, summed over ALL column shards by the caller
-  float s;
-  DropMask drop;          // NORM_ACC: message dropout of the product before it is stored / normalised (lightgcn.py:56);
-                          // NORMBWD: the same mask on the gradient leaving this layer.  p = 0: off
+  float* Y = nullptr;           // [n_rows, D] product (or gradient) out
+  float* inv_norm = nullptr;    // NORM_ACC: out; NORMBWD / NORMBWD_DOT: in; SS: out = this shard's sum of squares per row
+  float* accum = nullptr;       // NORM_ACC: accum += s * normalize(y)
+  const float* Xraw = nullptr;  // NORMBWD
+  const float* B = nullptr;     // NORMBWD / NORMBWD_DOT: dZ ; AXPY: B
+  const float* dot = nullptr;   // NORMBWD_DOT: z . (s dZ) per row, summed over ALL column shards by the caller
+  float s = 0.f;
+  DropMask drop = DropMask{0.f, 0};   // NORM_ACC: message dropout of the product before it is stored / normalised
+                                      // (lightgcn.py:56); NORMBWD: the same mask on the gradient leaving this layer.  p = 0: off
   // Row-sparse operand (the gradient at the start of the backward chain is non-zero on the <= 3 B batch rows only, and
   // one hop later on their neighbours): in_flags[c] != 0 iff row c of the gathered matrix has a non-zero; rows flagged
   // zero are not fetched (a x 0 adds exactly 0, so the result is unchanged).  *in_count = number of flagged rows; the
   // flags are consulted only while they cover less than 4/5 of the rows (each check is an extra L2 read per stored entry).
   // out_flags: the same for this product's output.
-  const uint8_t* in_flags;
-  const unsigned* in_count;
-  uint8_t* out_flags;
+  const uint8_t* in_flags = nullptr;
+  const unsigned* in_count = nullptr;
+  uint8_t* out_flags = nullptr;
   // Output rows to compute (NORM_ACC): row r is skipped entirely when row_mask[r] == 0 -- its outputs are neither
   // written nor accumulated.  nullptr = every row.  The last forward layer is needed on the batch rows only and the one
   // before it on their neighbours (lightgcn.py: the loss reads `out` at the batch rows).
-  const uint8_t* row_mask;
+  const uint8_t* row_mask = nullptr;
   // NORMBWD / AXPY: b_flags[r] == 0 promises that row r of B (dZ) is zero, so the row's epilogue term vanishes and
   // neither B nor X_raw is read for it (the BPR gradient w.r.t. the layer mean lives on the <= 3 B batch rows).
   // nullptr = read every row.
-  const uint8_t* b_flags;
+  const uint8_t* b_flags = nullptr;
   // AXPY: when adam.p is set the row's result is the gradient of parameter row r and is consumed on the spot -- the
   // Adam update of that row (torch's operation order, common.h) replaces the store to Y, which may then be null.  Saves
   // the gradient's round trip through memory and the optimizer's own launch (the last hop of a LightGCN step).
@@ -1378,109 +1378,74 @@ int tagrec::ensure_slab(const tagrec_graph* g, int D) {
 
 namespace {
 
-// the edge-dropout forms of launch_vec's three gather kernels (ed != nullptr); the fold of the long rows is shared
-template <int LPR, int EPI>
-int launch_vec_edrop(const GraphView& gv, const float* X, const EpiArgs& e, const LongView& lv, unsigned blocks, int threads,
-                     const EdgeDrop& ed, hipStream_t s) {
-  if constexpr (EPI == EPI_NONE || EPI == EPI_NORM_ACC || EPI == EPI_NORMBWD || EPI == EPI_AXPY) {
-    if (!e.row_mask) {
-      spmm_rows_edrop_kernel<LPR, EPI><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
-      return TAGREC_OK;
-    }
-    if constexpr ((EPI == EPI_NORMBWD || EPI == EPI_AXPY) && LPR <= 32) {
-      if (e.in_flags && !e.in_count) {
-        constexpr int rows_per_block = kWavesPerBlock * (kWave / LPR);
-        const unsigned gblocks = static_cast<unsigned>((gv.n_rows + rows_per_block - 1) / rows_per_block);
-        spmm_rows_grouped_edrop_kernel<LPR, EPI><<<gblocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
-        return TAGREC_OK;
-      }
-    }
-    spmm_rows_edrop_kernel<LPR, EPI, true><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, ed);
-    return TAGREC_OK;
-  } else {
-    return fail(TAGREC_E_UNSUPPORTED, "edge dropout: not available for this product");
-  }
+constexpr int kVecThreads = kWavesPerBlock * kWave;
+
+// the epilogues whose gather kernels are built in an edge-dropout form as well
+constexpr bool has_edrop_form(int epi) { return epi == EPI_NONE || epi == EPI_NORM_ACC || epi == EPI_NORMBWD || epi == EPI_AXPY; }
+
+// the fold of the long rows behind every gather kernel that fills the slab
+template <int LPR, int EPI, bool MASKED = false>
+void launch_finish(const tagrec_graph* g, const GraphView& gv, const EpiArgs& e, hipStream_t s) {
+  spmm_finish_kernel<LPR, EPI, MASKED><<<row_blocks(g->n_long), kVecThreads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
 }
 
+// One vector product: ONE choice of gather kernel -- every row, the masked rows (rows whose mask byte is 0 are left alone:
+// a separate instantiation) or the lane-grouped masked hop, each plain or in its edge-dropout form (ed != nullptr) -- and
+// the shared fold of the long rows.  check_spmm has refused what no kernel here covers.
 template <int LPR, int EPI>
-int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStream_t s, const EdgeDrop* ed = nullptr) {
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const int threads = kWavesPerBlock * kWave;
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
-  if (g->n_long > 0) {
-    int rc = ensure_slab(g, LPR * 4);
-    if (rc != TAGREC_OK) return rc;
-    lv.slab = g->slab;
-    lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-  }
-  if (ed) {
-    int rc = launch_vec_edrop<LPR, EPI>(gv, X, e, lv, blocks, threads, *ed, s);
-    if (rc != TAGREC_OK) return rc;
-    TAGREC_LAUNCH_CHECK();
-    if (g->n_long > 0) {
-      const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-      if (e.row_mask) spmm_finish_kernel<LPR, EPI, true><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-      else spmm_finish_kernel<LPR, EPI><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-      TAGREC_LAUNCH_CHECK();
-    }
-    return TAGREC_OK;
-  }
-  if (e.row_mask) {                       // rows whose mask byte is 0 are left alone (a separate instantiation)
-    constexpr bool kGroupable = (EPI == EPI_NORMBWD || EPI == EPI_AXPY) && LPR <= 32;
-    bool grouped = false;
-    if constexpr (kGroupable) {
-      // flags always consulted (in_count == NULL) = the hop below the top layer: a handful of flagged operand rows
-      if (e.in_flags && !e.in_count && !e.adam.p) {
-        constexpr int rows_per_block = kWavesPerBlock * (kWave / LPR);
-        const unsigned gblocks = static_cast<unsigned>((g->n_rows + rows_per_block - 1) / rows_per_block);
-        spmm_rows_grouped_kernel<LPR, EPI><<<gblocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv);
-        grouped = true;
-      }
-    }
-    if (!grouped) spmm_rows_kernel<LPR, EPI, true><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv);
-    TAGREC_LAUNCH_CHECK();
-    if (g->n_long > 0) {
-      const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-      spmm_finish_kernel<LPR, EPI, true><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-      TAGREC_LAUNCH_CHECK();
-    }
-    return TAGREC_OK;
-  }
-  spmm_rows_kernel<LPR, EPI><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv);
-  TAGREC_LAUNCH_CHECK();
-  if (g->n_long > 0) {
-    const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-    spmm_finish_kernel<LPR, EPI><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-    TAGREC_LAUNCH_CHECK();
-  }
-  return TAGREC_OK;
+int launch_vec(const tagrec_graph* g, const float* X, const EpiArgs& e, hipStream_t s, const EdgeDrop* ed) {
+  constexpr bool kGroupable = (EPI == EPI_NORMBWD || EPI == EPI_AXPY) && LPR <= 32;
+  const GraphView gv = view_of(g);
+  const bool masked = e.row_mask != nullptr;
+  // flags always consulted (in_count == NULL) = the hop below the top layer: a handful of flagged operand rows
+  const bool grouped = kGroupable && masked && e.in_flags && !e.in_count && !e.adam.p;
+  return launch_with_long_rows(
+      g, LPR * 4,
+      [&](const LongView& lv) {
+        if constexpr (kGroupable) {
+          if (grouped) {
+            const unsigned grid = row_blocks(g->n_rows, kWavesPerBlock * (kWave / LPR)) + lv.chunk_blocks;
+            if (ed) spmm_rows_grouped_edrop_kernel<LPR, EPI><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv, *ed);
+            else spmm_rows_grouped_kernel<LPR, EPI><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv);
+            return;
+          }
+        }
+        const unsigned grid = row_blocks(g->n_rows) + lv.chunk_blocks;
+        if constexpr (has_edrop_form(EPI)) {
+          if (ed) {
+            if (masked) spmm_rows_edrop_kernel<LPR, EPI, true><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv, *ed);
+            else spmm_rows_edrop_kernel<LPR, EPI><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv, *ed);
+            return;
+          }
+        }
+        if (masked) spmm_rows_kernel<LPR, EPI, true><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv);
+        else spmm_rows_kernel<LPR, EPI><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv);
+      },
+      [&] {
+        if (masked) launch_finish<LPR, EPI, true>(g, gv, e, s);
+        else launch_finish<LPR, EPI>(g, gv, e, s);
+      });
 }
 
+// Every host-side refusal of a product, before anything is launched.  *vec: the vector kernels take it (else the scalar one).
 template <int EPI>
-int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, void* stream, const char* who,
-                const EdgeDrop* ed = nullptr) {
+int check_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, const char* who, const EdgeDrop* ed, bool* vec) {
+  *vec = false;
   TAGREC_REQUIRE(g != nullptr, std::string(who) + ": null graph handle");
   TAGREC_REQUIRE(X != nullptr && e.Y != nullptr, std::string(who) + ": null X or output");
   TAGREC_REQUIRE(D >= 1, std::string(who) + ": D must be >= 1");
   TAGREC_REQUIRE(static_cast<const void*>(X) != static_cast<const void*>(e.Y), std::string(who) + ": output aliases the gathered input");
   if (g->n_rows == 0) return TAGREC_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
   bool vec_ok = aligned16(X) && aligned16(e.Y);
   if (e.accum) vec_ok = vec_ok && aligned16(e.accum);
   if (e.Xraw) vec_ok = vec_ok && aligned16(e.Xraw);
   if (e.B) vec_ok = vec_ok && aligned16(e.B);
   if (e.drop.p > 0.f && !vec_ok) return fail(TAGREC_E_INVALID, std::string(who) + ": dropout needs 16-byte aligned rows");
-  if (vec_ok) {
-    switch (D) {
-      case 8: return launch_vec<2, EPI>(g, X, e, s, ed);
-      case 16: return launch_vec<4, EPI>(g, X, e, s, ed);
-      case 32: return launch_vec<8, EPI>(g, X, e, s, ed);
-      case 64: return launch_vec<16, EPI>(g, X, e, s, ed);
-      case 128: return launch_vec<32, EPI>(g, X, e, s, ed);
-      case 256: return launch_vec<64, EPI>(g, X, e, s, ed);
-      default: break;
-    }
+  if (vec_ok && is_vec_width(D)) {
+    *vec = true;
+    if (g->n_long > 0) TAGREC_TRY(ensure_slab(g, D));
+    if (ed && !has_edrop_form(EPI)) return fail(TAGREC_E_UNSUPPORTED, "edge dropout: not available for this product");
+    return TAGREC_OK;
   }
   if (ed)       // the scalar kernel knows no edge mask: it would multiply by the un-dropped matrix
     return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": edge dropout needs the vector kernels (D in {8,...,256}, every operand "
@@ -1495,24 +1460,149 @@ int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, 
                                                      "every operand 16-byte aligned); the scalar kernel would ignore them");
   if (D > kMaxGenericBlocks * kWave)
     return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": row width " + std::to_string(D) + " > 512 is not covered");
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  spmm_rows_generic_kernel<EPI><<<blocks, kWavesPerBlock * kWave, 0, s>>>(gv, X, e, D);
+  return TAGREC_OK;
+}
+
+// The launches of a product that check_spmm has passed.
+template <int EPI>
+int run_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, void* stream, const char* who, const EdgeDrop* ed, bool vec) {
+  if (g->n_rows == 0) return TAGREC_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (vec) return vec_width_dispatch(D, who, [&](auto lc) { return launch_vec<decltype(lc)::value, EPI>(g, X, e, s, ed); });
+  spmm_rows_generic_kernel<EPI><<<row_blocks(g->n_rows), kVecThreads, 0, s>>>(view_of(g), X, e, D);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }
 
+template <int EPI>
+int launch_spmm(const tagrec_graph* g, const float* X, const EpiArgs& e, int D, void* stream, const char* who,
+                const EdgeDrop* ed = nullptr) {
+  bool vec;
+  TAGREC_TRY(check_spmm<EPI>(g, X, e, D, who, ed, &vec));
+  return run_spmm<EPI>(g, X, e, D, stream, who, ed, vec);
+}
+
+// ---- edge dropout inside the products (`node_drop`, /root/reference/model/help/adj.py:170-191; EdgeDrop in common.h) -------
+// The `_edrop` form of a product multiplies by the matrix whose entry (i, j) is dropped with probability ed_p under ed_seed and
+// otherwise scaled by 1 / (1 - ed_p); ed_transposed != 0: the handle holds the transpose of the matrix the mask is defined on.
+// A product and its `_edrop` twin share one body: ed == nullptr is the plain form, `who` the entry point's own name.
+
+// the width refusal of a vector-only product (TAGREC_E_INVALID) or, for its twin, the refusals of the edge-drop arguments
+int vec_args(const char* who, const EdgeDrop* ed, int D) {
+  if (!ed) {
+    TAGREC_REQUIRE(is_vec_width(D), std::string(who) + ": D must be 8 .. 256, a power of two");
+    return TAGREC_OK;
+  }
+  TAGREC_REQUIRE(ed->p >= 0.f && ed->p < 1.f, std::string(who) + ": edge-drop p must be in [0, 1)");
+  if (!is_vec_width(D))
+    return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": edge dropout needs a vector-kernel width (D must be 8 .. 256, a power of two)");
+  return TAGREC_OK;
+}
+
+int spmm_plain(const char* who, const tagrec_graph* g, const float* X, float* Y, int D, void* stream, const EdgeDrop* ed) {
+  if (ed) TAGREC_TRY(vec_args(who, ed, D));
+  EpiArgs e;
+  e.Y = Y;
+  return launch_spmm<EPI_NONE>(g, X, e, D, stream, who, ed);
+}
+
+// the NORM_ACC operands (drop.p = 0: no message dropout; row_mask == nullptr: every row)
+EpiArgs norm_acc_epi(float* Y_raw, float* inv_norm, float* acc, float acc_scale, DropMask drop, const uint8_t* row_mask) {
+  EpiArgs e;
+  e.Y = Y_raw; e.inv_norm = inv_norm; e.accum = acc; e.s = acc_scale; e.drop = drop; e.row_mask = row_mask;
+  return e;
+}
+
+int spmm_norm_acc_rows(const char* who, const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm, float* acc,
+                       float acc_scale, const uint8_t* row_mask, float drop_p, uint64_t seed, int D, void* stream, const EdgeDrop* ed) {
+  TAGREC_REQUIRE(inv_norm != nullptr, std::string(who) + ": null inv_norm");
+  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, std::string(who) + ": p must be in [0, 1)");
+  TAGREC_TRY(vec_args(who, ed, D));
+  const EpiArgs e = norm_acc_epi(Y_raw, inv_norm, acc, acc_scale, DropMask{drop_p, seed}, row_mask);
+  return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, who, ed);
+}
+
+// the NORMBWD / NORMBWD_DOT operands (dot == nullptr: NORMBWD)
+EpiArgs normbwd_epi(float* G_out, const float* X_raw, const float* inv_norm, const float* dZ, const float* dot, float d_scale) {
+  EpiArgs e;
+  e.Y = G_out; e.inv_norm = const_cast<float*>(inv_norm); e.Xraw = X_raw; e.B = dZ; e.dot = dot; e.s = d_scale;
+  return e;
+}
+
+int spmm_normbwd_sparse(const char* who, const tagrec_graph* g, const float* G_in, const uint8_t* in_flags, const unsigned* in_count,
+                        const float* X_raw, const float* inv_norm, const float* dZ, float d_scale, float drop_p, uint64_t seed,
+                        float* G_out, uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask, const uint8_t* dz_flags, int D,
+                        void* stream, const EdgeDrop* ed) {
+  TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, std::string(who) + ": null X_raw, inv_norm or dZ");
+  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, std::string(who) + ": in_count without in_flags");
+  TAGREC_REQUIRE((out_flags == nullptr) == (out_count == nullptr), std::string(who) + ": out_flags and out_count go together");
+  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, std::string(who) + ": p must be in [0, 1)");
+  TAGREC_TRY(vec_args(who, ed, D));
+  EpiArgs e = normbwd_epi(G_out, X_raw, inv_norm, dZ, nullptr, d_scale);
+  e.drop = DropMask{drop_p, seed};
+  e.in_flags = in_flags; e.in_count = in_count; e.out_flags = out_flags; e.row_mask = row_mask; e.b_flags = dz_flags;
+  const int rc = launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, who, ed);
+  if (rc != TAGREC_OK || !out_flags) return rc;
+  return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
+}
+
+// the AXPY operands
+EpiArgs axpy_epi(float* G_out, const float* B, float b_scale, const uint8_t* in_flags, const unsigned* in_count, const uint8_t* b_flags) {
+  EpiArgs e;
+  e.Y = G_out; e.B = B; e.s = b_scale; e.in_flags = in_flags; e.in_count = in_count; e.b_flags = b_flags;
+  return e;
+}
+
+int spmm_axpy_sparse(const char* who, const tagrec_graph* g, const float* G_in, const uint8_t* in_flags, const unsigned* in_count,
+                     const float* B, float b_scale, float* G_out, const uint8_t* row_mask, const uint8_t* b_flags, int D, void* stream,
+                     const EdgeDrop* ed) {
+  TAGREC_REQUIRE(B != nullptr, std::string(who) + ": null B");
+  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, std::string(who) + ": in_count without in_flags");
+  TAGREC_TRY(vec_args(who, ed, D));
+  EpiArgs e = axpy_epi(G_out, B, b_scale, in_flags, in_count, b_flags);
+  e.row_mask = row_mask;
+  return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, who, ed);
+}
+
+// What the two Adam entry points require of the hop and its operands, and the epilogue they share (AdamRow in common.h).
+int adam_hop_args(const char* who, const float* G_in, const uint8_t* in_flags, const unsigned* in_count, const float* B, const float* p,
+                  const float* m, const float* v, int D) {
+  TAGREC_REQUIRE(B != nullptr && p != nullptr && m != nullptr && v != nullptr, std::string(who) + ": null pointer");
+  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, std::string(who) + ": in_count without in_flags");
+  TAGREC_REQUIRE(is_vec_width(D), std::string(who) + ": D must be 8 .. 256, a power of two");
+  TAGREC_REQUIRE(static_cast<const void*>(G_in) != static_cast<const void*>(p), std::string(who) + ": the gathered operand aliases the parameters");
+  TAGREC_REQUIRE(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(G_in) && aligned16(B),
+                 std::string(who) + ": every operand (p, m, v, G_in, B) must be 16-byte aligned");
+  return TAGREC_OK;
+}
+
+// step_size / bc2_sqrt: the two step-dependent factors, read from coef_dev instead when that is set
+EpiArgs adam_hop_epi(const uint8_t* in_flags, const unsigned* in_count, const float* B, float b_scale, const uint8_t* b_flags, float* p,
+                     float* m, float* v, float b1, float b2, float eps, float step_size, float bc2_sqrt, const float* coef_dev) {
+  EpiArgs e = axpy_epi(p, B, b_scale, in_flags, in_count, b_flags);
+  e.adam = AdamRow{p, m, v, static_cast<float>(1.0 - static_cast<double>(b1)), b2, static_cast<float>(1.0 - static_cast<double>(b2)),
+                   step_size, bc2_sqrt, eps, coef_dev};
+  return e;
+}
+
+EdgeDrop edge_drop(float ed_p, uint64_t ed_seed, int ed_transposed) { return EdgeDrop{ed_p, ed_seed, ed_transposed != 0}; }
+
 }  // namespace
 
 extern "C" int tagrec_spmm_f32(const tagrec_graph* g, const float* X, float* Y, int D, void* stream) {
-  EpiArgs e{Y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
-  return launch_spmm<EPI_NONE>(g, X, e, D, stream, "spmm");
+  return spmm_plain("spmm", g, X, Y, D, stream, nullptr);
+}
+
+extern "C" int tagrec_spmm_edrop_f32(const tagrec_graph* g, const float* X, float* Y, float ed_p, uint64_t ed_seed,
+                                     int ed_transposed, int D, void* stream) {
+  const EdgeDrop ed = edge_drop(ed_p, ed_seed, ed_transposed);
+  return spmm_plain("spmm_edrop", g, X, Y, D, stream, &ed);
 }
 
 extern "C" int tagrec_spmm_norm_acc_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
                                         float* acc, float acc_scale, int D, void* stream) {
   TAGREC_REQUIRE(inv_norm != nullptr && acc != nullptr, "spmm_norm_acc: null inv_norm or acc");
-  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = norm_acc_epi(Y_raw, inv_norm, acc, acc_scale, DropMask{0.f, 0}, nullptr);
   return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, "spmm_norm_acc");
 }
 
@@ -1520,20 +1610,21 @@ extern "C" int tagrec_spmm_normbwd_f32(const tagrec_graph* g, const float* G_in,
                                        const float* inv_norm, const float* dZ, float d_scale, float* G_out,
                                        int D, void* stream) {
   TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, "spmm_normbwd: null X_raw, inv_norm or dZ");
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, nullptr, d_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = normbwd_epi(G_out, X_raw, inv_norm, dZ, nullptr, d_scale);
   return launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, "spmm_normbwd");
 }
 
 extern "C" int tagrec_spmm_axpy_f32(const tagrec_graph* g, const float* G_in, const float* B, float b_scale,
                                     float* G_out, int D, void* stream) {
   TAGREC_REQUIRE(B != nullptr, "spmm_axpy: null B");
-  EpiArgs e{G_out, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = axpy_epi(G_out, B, b_scale, nullptr, nullptr, nullptr);
   return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy");
 }
 
 extern "C" int tagrec_spmm_ss_f32(const tagrec_graph* g, const float* X, float* Y, float* ss, int D, void* stream) {
   TAGREC_REQUIRE(ss != nullptr, "spmm_ss: null ss");
-  EpiArgs e{Y, ss, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  EpiArgs e;
+  e.Y = Y; e.inv_norm = ss;
   return launch_spmm<EPI_SS>(g, X, e, D, stream, "spmm_ss");
 }
 
@@ -1542,7 +1633,7 @@ extern "C" int tagrec_spmm_normbwd_dot_f32(const tagrec_graph* g, const float* G
                                            float* G_out, int D, void* stream) {
   TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr && dot != nullptr,
                  "spmm_normbwd_dot: null X_raw, inv_norm, dZ or dot");
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, dot, d_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = normbwd_epi(G_out, X_raw, inv_norm, dZ, dot, d_scale);
   return launch_spmm<EPI_NORMBWD_DOT>(g, G_in, e, D, stream, "spmm_normbwd_dot");
 }
 
@@ -1552,7 +1643,7 @@ extern "C" int tagrec_spmm_norm_acc_drop_f32(const tagrec_graph* g, const float*
   TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_norm_acc_drop: p must be in [0, 1)");
   TAGREC_REQUIRE(drop_p == 0.f || (D % 4 == 0 && D <= 256 && (D & (D - 1)) == 0 && D >= 8),
                  "spmm_norm_acc_drop: dropout needs a vector-kernel width (8..256, power of two)");
-  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{drop_p, seed}, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = norm_acc_epi(Y_raw, inv_norm, acc, acc_scale, DropMask{drop_p, seed}, nullptr);
   return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, "spmm_norm_acc_drop");
 }
 
@@ -1563,7 +1654,8 @@ extern "C" int tagrec_spmm_normbwd_drop_f32(const tagrec_graph* g, const float* 
   TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_normbwd_drop: p must be in [0, 1)");
   TAGREC_REQUIRE(drop_p == 0.f || (D % 4 == 0 && D <= 256 && (D & (D - 1)) == 0 && D >= 8),
                  "spmm_normbwd_drop: dropout needs a vector-kernel width (8..256, power of two)");
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, nullptr, d_scale, DropMask{drop_p, seed}, nullptr, nullptr, nullptr, nullptr};
+  EpiArgs e = normbwd_epi(G_out, X_raw, inv_norm, dZ, nullptr, d_scale);
+  e.drop = DropMask{drop_p, seed};
   return launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, "spmm_normbwd_drop");
 }
 
@@ -1573,25 +1665,33 @@ extern "C" int tagrec_spmm_normbwd_sparse_f32(const tagrec_graph* g, const float
                                               const float* dZ, float d_scale, float drop_p, uint64_t seed, float* G_out,
                                               uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask,
                                               const uint8_t* dz_flags, int D, void* stream) {
-  TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, "spmm_normbwd_sparse: null X_raw, inv_norm or dZ");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_normbwd_sparse: in_count without in_flags");
-  TAGREC_REQUIRE((out_flags == nullptr) == (out_count == nullptr), "spmm_normbwd_sparse: out_flags and out_count go together");
-  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_normbwd_sparse: p must be in [0, 1)");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_normbwd_sparse: D must be 8 .. 256, a power of two");
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, nullptr, d_scale, DropMask{drop_p, seed}, in_flags, in_count, out_flags, row_mask, dz_flags};
-  int rc = launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, "spmm_normbwd_sparse");
-  if (rc != TAGREC_OK || !out_flags) return rc;
-  return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
+  return spmm_normbwd_sparse("spmm_normbwd_sparse", g, G_in, in_flags, in_count, X_raw, inv_norm, dZ, d_scale, drop_p, seed, G_out,
+                             out_flags, out_count, row_mask, dz_flags, D, stream, nullptr);
+}
+
+extern "C" int tagrec_spmm_normbwd_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                                    const unsigned* in_count, const float* X_raw, const float* inv_norm,
+                                                    const float* dZ, float d_scale, float drop_p, uint64_t seed, float* G_out,
+                                                    uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask,
+                                                    const uint8_t* dz_flags, float ed_p, uint64_t ed_seed, int ed_transposed,
+                                                    int D, void* stream) {
+  const EdgeDrop ed = edge_drop(ed_p, ed_seed, ed_transposed);
+  return spmm_normbwd_sparse("spmm_normbwd_sparse_edrop", g, G_in, in_flags, in_count, X_raw, inv_norm, dZ, d_scale, drop_p, seed,
+                             G_out, out_flags, out_count, row_mask, dz_flags, D, stream, &ed);
 }
 
 extern "C" int tagrec_spmm_axpy_sparse_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
                                            const unsigned* in_count, const float* B, float b_scale, float* G_out,
                                            const uint8_t* row_mask, const uint8_t* b_flags, int D, void* stream) {
-  TAGREC_REQUIRE(B != nullptr, "spmm_axpy_sparse: null B");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_axpy_sparse: in_count without in_flags");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_axpy_sparse: D must be 8 .. 256, a power of two");
-  EpiArgs e{G_out, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, in_flags, in_count, nullptr, row_mask, b_flags};
-  return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy_sparse");
+  return spmm_axpy_sparse("spmm_axpy_sparse", g, G_in, in_flags, in_count, B, b_scale, G_out, row_mask, b_flags, D, stream, nullptr);
+}
+
+extern "C" int tagrec_spmm_axpy_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
+                                                 const unsigned* in_count, const float* B, float b_scale, float* G_out,
+                                                 const uint8_t* row_mask, const uint8_t* b_flags, float ed_p, uint64_t ed_seed,
+                                                 int ed_transposed, int D, void* stream) {
+  const EdgeDrop ed = edge_drop(ed_p, ed_seed, ed_transposed);
+  return spmm_axpy_sparse("spmm_axpy_sparse_edrop", g, G_in, in_flags, in_count, B, b_scale, G_out, row_mask, b_flags, D, stream, &ed);
 }
 
 // The last hop of a training step with the optimizer folded in: row r of (A G_in + b_scale B) is the gradient of
@@ -1601,41 +1701,31 @@ extern "C" int tagrec_spmm_axpy_adam_f32(const tagrec_graph* g, const float* G_i
                                          const unsigned* in_count, const float* B, float b_scale, const uint8_t* b_flags,
                                          float* p, float* m, float* v, float lr, float b1, float b2, float eps, int64_t step,
                                          int D, void* stream) {
-  TAGREC_REQUIRE(B != nullptr && p != nullptr && m != nullptr && v != nullptr, "spmm_axpy_adam: null pointer");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_axpy_adam: in_count without in_flags");
+  TAGREC_TRY(adam_hop_args("spmm_axpy_adam", G_in, in_flags, in_count, B, p, m, v, D));
   TAGREC_REQUIRE(step >= 1, "spmm_axpy_adam: step counts from 1");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_axpy_adam: D must be 8 .. 256, a power of two");
-  TAGREC_REQUIRE(static_cast<const void*>(G_in) != static_cast<const void*>(p), "spmm_axpy_adam: the gathered operand aliases the parameters");
-  TAGREC_REQUIRE(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(G_in) && aligned16(B),
-                 "spmm_axpy_adam: every operand (p, m, v, G_in, B) must be 16-byte aligned");
   const double bc1 = 1.0 - pow(static_cast<double>(b1), static_cast<double>(step));      // as tagrec_adam_f32
   const double bc2 = 1.0 - pow(static_cast<double>(b2), static_cast<double>(step));
-  EpiArgs e{p, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, in_flags, in_count, nullptr, nullptr, b_flags};
-  e.adam = AdamRow{p, m, v, static_cast<float>(1.0 - static_cast<double>(b1)), b2, static_cast<float>(1.0 - static_cast<double>(b2)),
-                   static_cast<float>(static_cast<double>(lr) / bc1), static_cast<float>(sqrt(bc2)), eps};
+  const EpiArgs e = adam_hop_epi(in_flags, in_count, B, b_scale, b_flags, p, m, v, b1, b2, eps,
+                                 static_cast<float>(static_cast<double>(lr) / bc1), static_cast<float>(sqrt(bc2)), nullptr);
   return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy_adam");
 }
 
 // The same with the step counter and the two step-dependent factors in DEVICE memory (advanced by a one-thread kernel in
 // front of the product), so the whole training step -- optimizer included -- can be captured once as a HIP graph and replayed.
+// The counter moves only once nothing on the host can refuse the product any more: a refused call leaves it where it was.
 extern "C" int tagrec_adam_advance(int64_t* step_dev, float* coef_dev, float lr, float b1, float b2, void* stream);
 extern "C" int tagrec_spmm_axpy_adam_graph_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
                                                const unsigned* in_count, const float* B, float b_scale, const uint8_t* b_flags,
                                                float* p, float* m, float* v, float lr, float b1, float b2, float eps,
                                                int64_t* step_dev, float* coef_dev, int D, void* stream) {
-  TAGREC_REQUIRE(B != nullptr && p != nullptr && m != nullptr && v != nullptr && step_dev != nullptr && coef_dev != nullptr,
-                 "spmm_axpy_adam_graph: null pointer");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_axpy_adam_graph: in_count without in_flags");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_axpy_adam_graph: D must be 8 .. 256, a power of two");
-  TAGREC_REQUIRE(static_cast<const void*>(G_in) != static_cast<const void*>(p), "spmm_axpy_adam_graph: the gathered operand aliases the parameters");
-  TAGREC_REQUIRE(aligned16(p) && aligned16(m) && aligned16(v) && aligned16(G_in) && aligned16(B),
-                 "spmm_axpy_adam_graph: every operand (p, m, v, G_in, B) must be 16-byte aligned");
-  int rc = tagrec_adam_advance(step_dev, coef_dev, lr, b1, b2, stream);
-  if (rc != TAGREC_OK) return rc;
-  EpiArgs e{p, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, in_flags, in_count, nullptr, nullptr, b_flags};
-  e.adam = AdamRow{p, m, v, static_cast<float>(1.0 - static_cast<double>(b1)), b2, static_cast<float>(1.0 - static_cast<double>(b2)),
-                   0.f, 1.f, eps, coef_dev};
-  return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy_adam_graph");
+  const char* who = "spmm_axpy_adam_graph";
+  TAGREC_REQUIRE(step_dev != nullptr && coef_dev != nullptr, "spmm_axpy_adam_graph: null pointer");
+  TAGREC_TRY(adam_hop_args(who, G_in, in_flags, in_count, B, p, m, v, D));
+  const EpiArgs e = adam_hop_epi(in_flags, in_count, B, b_scale, b_flags, p, m, v, b1, b2, eps, 0.f, 1.f, coef_dev);
+  bool vec;
+  TAGREC_TRY(check_spmm<EPI_AXPY>(g, G_in, e, D, who, nullptr, &vec));
+  TAGREC_TRY(tagrec_adam_advance(step_dev, coef_dev, lr, b1, b2, stream));
+  return run_spmm<EPI_AXPY>(g, G_in, e, D, stream, who, nullptr, vec);
 }
 
 extern "C" int tagrec_spmm_normbwd_dot_sparse_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
@@ -1647,9 +1737,10 @@ extern "C" int tagrec_spmm_normbwd_dot_sparse_f32(const tagrec_graph* g, const f
                  "spmm_normbwd_dot_sparse: null X_raw, inv_norm, dZ or dot");
   TAGREC_REQUIRE(in_flags != nullptr && in_count != nullptr, "spmm_normbwd_dot_sparse: null in_flags or in_count");
   TAGREC_REQUIRE((out_flags == nullptr) == (out_count == nullptr), "spmm_normbwd_dot_sparse: out_flags and out_count go together");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_normbwd_dot_sparse: D must be 8 .. 256, a power of two");
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, dot, d_scale, DropMask{0.f, 0}, in_flags, in_count, out_flags, row_mask};
-  int rc = launch_spmm<EPI_NORMBWD_DOT>(g, G_in, e, D, stream, "spmm_normbwd_dot_sparse");
+  TAGREC_REQUIRE(is_vec_width(D), "spmm_normbwd_dot_sparse: D must be 8 .. 256, a power of two");
+  EpiArgs e = normbwd_epi(G_out, X_raw, inv_norm, dZ, dot, d_scale);
+  e.in_flags = in_flags; e.in_count = in_count; e.out_flags = out_flags; e.row_mask = row_mask;
+  const int rc = launch_spmm<EPI_NORMBWD_DOT>(g, G_in, e, D, stream, "spmm_normbwd_dot_sparse");
   if (rc != TAGREC_OK || !out_flags) return rc;
   return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
 }
@@ -1662,9 +1753,10 @@ extern "C" int tagrec_spmm_flags_f32(const tagrec_graph* g, const float* G_in, c
                                      void* stream) {
   TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_flags: in_count without in_flags");
   TAGREC_REQUIRE(out_flags != nullptr || out_count == nullptr, "spmm_flags: out_count without out_flags");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_flags: D must be 8 .. 256, a power of two");
-  EpiArgs e{G_out, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, in_flags, in_count, out_flags, row_mask, nullptr};
-  int rc = launch_spmm<EPI_NONE>(g, G_in, e, D, stream, "spmm_flags");
+  TAGREC_REQUIRE(is_vec_width(D), "spmm_flags: D must be 8 .. 256, a power of two");
+  EpiArgs e;
+  e.Y = G_out; e.in_flags = in_flags; e.in_count = in_count; e.out_flags = out_flags; e.row_mask = row_mask;
+  const int rc = launch_spmm<EPI_NONE>(g, G_in, e, D, stream, "spmm_flags");
   if (rc != TAGREC_OK || !out_count) return rc;
   return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
 }
@@ -1676,8 +1768,7 @@ extern "C" int tagrec_graph_mark_rows_u8(const tagrec_graph* g, const int64_t* r
   TAGREC_REQUIRE(g->n_rows == g->n_cols, "graph_mark_rows: square adjacency expected (flags are indexed by node)");
   TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), "graph_mark_rows: bad row count");
   if (n_listed == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  mark_rows_kernel<true><<<static_cast<unsigned>(n_listed * kListedSplits), 256, 0, static_cast<hipStream_t>(stream)>>>(gv, rows, n_listed, flags);
+  mark_rows_kernel<true><<<static_cast<unsigned>(n_listed * kListedSplits), 256, 0, static_cast<hipStream_t>(stream)>>>(view_of(g), rows, n_listed, flags);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }
@@ -1687,8 +1778,7 @@ extern "C" int tagrec_graph_mark_cols_u8(const tagrec_graph* g, const int64_t* r
   TAGREC_REQUIRE(g != nullptr && flags != nullptr && (n_listed == 0 || rows != nullptr), "graph_mark_cols: null pointer");
   TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), "graph_mark_cols: bad row count");
   if (n_listed == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  mark_rows_kernel<false><<<static_cast<unsigned>(n_listed * kListedSplits), 256, 0, static_cast<hipStream_t>(stream)>>>(gv, rows, n_listed, flags);
+  mark_rows_kernel<false><<<static_cast<unsigned>(n_listed * kListedSplits), 256, 0, static_cast<hipStream_t>(stream)>>>(view_of(g), rows, n_listed, flags);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }
@@ -1697,59 +1787,71 @@ extern "C" int64_t tagrec_spmm_listed_workspace(int64_t n_listed, int D) {
   return n_listed < 0 || D < 1 ? 0 : n_listed * kListedSplits * static_cast<int64_t>(D);
 }
 
-extern "C" int tagrec_spmm_listed_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
-                                      int D, float* ws, int64_t ws_floats, void* stream) {
-  TAGREC_REQUIRE(g != nullptr && X != nullptr && Y != nullptr && (n_listed == 0 || rows != nullptr), "spmm_listed: null pointer");
-  TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), "spmm_listed: bad row count");
-  TAGREC_REQUIRE(aligned16(X) && aligned16(Y) && aligned16(ws), "spmm_listed: rows must be 16-byte aligned");
+namespace {
+int spmm_listed(const char* who, const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y, int D, float* ws,
+                int64_t ws_floats, void* stream, const EdgeDrop* ed) {
+  TAGREC_REQUIRE(g != nullptr && X != nullptr && Y != nullptr && (n_listed == 0 || rows != nullptr), std::string(who) + ": null pointer");
+  TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), std::string(who) + ": bad row count");
+  TAGREC_REQUIRE(aligned16(X) && aligned16(Y) && aligned16(ws), std::string(who) + ": rows must be 16-byte aligned");
   TAGREC_REQUIRE(n_listed == 0 || (ws != nullptr && ws_floats >= tagrec_spmm_listed_workspace(n_listed, D)),
-                 "spmm_listed: workspace smaller than tagrec_spmm_listed_workspace(n_listed, D)");
+                 std::string(who) + ": workspace smaller than tagrec_spmm_listed_workspace(n_listed, D)");
+  if (ed) TAGREC_TRY(vec_args(who, ed, D));
   if (n_listed == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
+  const GraphView gv = view_of(g);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned blocks = static_cast<unsigned>(n_listed * kListedSplits);
-  const int threads = kWavesPerBlock * kWave;
-#define LISTED(L)                                                                                   \
-  spmm_listed_kernel<L><<<blocks, threads, 0, s>>>(gv, rows, X, ws);                                \
-  TAGREC_LAUNCH_CHECK();                                                                            \
-  spmm_listed_fold_kernel<L><<<static_cast<unsigned>((n_listed * L + 255) / 256), 256, 0, s>>>(ws, Y, n_listed); \
-  break
-  switch (D) {
-    case 8: LISTED(2);
-    case 16: LISTED(4);
-    case 32: LISTED(8);
-    case 64: LISTED(16);
-    case 128: LISTED(32);
-    case 256: LISTED(64);
-    default: return fail(TAGREC_E_UNSUPPORTED, "spmm_listed: D must be 8 .. 256, a power of two");
-  }
-#undef LISTED
-  TAGREC_LAUNCH_CHECK();
-  return TAGREC_OK;
+  return vec_width_dispatch(D, who, [&](auto lc) {
+    constexpr int LPR = decltype(lc)::value;
+    if (ed) spmm_listed_edrop_kernel<LPR><<<blocks, kVecThreads, 0, s>>>(gv, rows, X, ws, *ed);
+    else spmm_listed_kernel<LPR><<<blocks, kVecThreads, 0, s>>>(gv, rows, X, ws);
+    TAGREC_LAUNCH_CHECK();
+    spmm_listed_fold_kernel<LPR><<<row_blocks(n_listed * LPR, 256), 256, 0, s>>>(ws, Y, n_listed);
+    TAGREC_LAUNCH_CHECK();
+    return TAGREC_OK;
+  });
+}
+}  // namespace
+
+extern "C" int tagrec_spmm_listed_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
+                                      int D, float* ws, int64_t ws_floats, void* stream) {
+  return spmm_listed("spmm_listed", g, rows, n_listed, X, Y, D, ws, ws_floats, stream, nullptr);
+}
+
+extern "C" int tagrec_spmm_listed_edrop_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
+                                            int D, float* ws, int64_t ws_floats, float ed_p, uint64_t ed_seed, int ed_transposed,
+                                            void* stream) {
+  const EdgeDrop ed = edge_drop(ed_p, ed_seed, ed_transposed);
+  return spmm_listed("spmm_listed_edrop", g, rows, n_listed, X, Y, D, ws, ws_floats, stream, &ed);
 }
 
 extern "C" int tagrec_spmm_norm_acc_rows_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
                                              float* acc, float acc_scale, const uint8_t* row_mask, float drop_p,
                                              uint64_t seed, int D, void* stream) {
-  TAGREC_REQUIRE(inv_norm != nullptr, "spmm_norm_acc_rows: null inv_norm");
-  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_norm_acc_rows: p must be in [0, 1)");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_norm_acc_rows: D must be 8 .. 256, a power of two");
-  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{drop_p, seed}, nullptr, nullptr, nullptr, row_mask, nullptr};
-  return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, "spmm_norm_acc_rows");
+  return spmm_norm_acc_rows("spmm_norm_acc_rows", g, X, Y_raw, inv_norm, acc, acc_scale, row_mask, drop_p, seed, D, stream, nullptr);
+}
+
+extern "C" int tagrec_spmm_norm_acc_rows_edrop_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
+                                                   float* acc, float acc_scale, const uint8_t* row_mask, float drop_p,
+                                                   uint64_t seed, float ed_p, uint64_t ed_seed, int ed_transposed, int D,
+                                                   void* stream) {
+  const EdgeDrop ed = edge_drop(ed_p, ed_seed, ed_transposed);
+  return spmm_norm_acc_rows("spmm_norm_acc_rows_edrop", g, X, Y_raw, inv_norm, acc, acc_scale, row_mask, drop_p, seed, D, stream, &ed);
 }
 
 extern "C" int tagrec_spmm_rows_f32(const tagrec_graph* g, const float* X, float* Y, const uint8_t* row_mask, int D, void* stream) {
   TAGREC_REQUIRE(row_mask != nullptr, "spmm_rows: null row_mask");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_rows: D must be 8 .. 256, a power of two");
-  EpiArgs e{Y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask};
+  TAGREC_REQUIRE(is_vec_width(D), "spmm_rows: D must be 8 .. 256, a power of two");
+  EpiArgs e;
+  e.Y = Y; e.row_mask = row_mask;
   return launch_spmm<EPI_NONE>(g, X, e, D, stream, "spmm_rows");
 }
 
 extern "C" int tagrec_spmm_ss_rows_f32(const tagrec_graph* g, const float* X, float* Y, float* ss, const uint8_t* row_mask, int D,
                                        void* stream) {
   TAGREC_REQUIRE(ss != nullptr && row_mask != nullptr, "spmm_ss_rows: null ss or row_mask");
-  TAGREC_REQUIRE(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256, "spmm_ss_rows: D must be 8 .. 256, a power of two");
-  EpiArgs e{Y, ss, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask};
+  TAGREC_REQUIRE(is_vec_width(D), "spmm_ss_rows: D must be 8 .. 256, a power of two");
+  EpiArgs e;
+  e.Y = Y; e.inv_norm = ss; e.row_mask = row_mask;
   return launch_spmm<EPI_SS>(g, X, e, D, stream, "spmm_ss_rows");
 }
 
@@ -1758,33 +1860,27 @@ namespace {
 int noise_args(const char* who, float eps, int view, int layer, int D) {
   TAGREC_REQUIRE(eps >= 0.f && eps < INFINITY, std::string(who) + ": eps must be finite and >= 0");
   TAGREC_REQUIRE(view >= 0 && layer >= 0, std::string(who) + ": view and layer must be >= 0");
-  if (!(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256))
+  if (!is_vec_width(D))
     return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": the noise forms need a vector-kernel width (D must be 8 .. 256, a power of two)");
   return TAGREC_OK;
 }
 
 template <int LPR>
 int launch_vec_noise(const tagrec_graph* g, const float* X, const EpiArgs& e, const NoiseDir& nd, hipStream_t s) {
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const int threads = kWavesPerBlock * kWave;
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
-  if (g->n_long > 0) {
-    int rc = ensure_slab(g, LPR * 4);
-    if (rc != TAGREC_OK) return rc;
-    lv.slab = g->slab;
-    lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-  }
-  if (e.row_mask) spmm_rows_noise_kernel<LPR, true><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, nd);
-  else spmm_rows_noise_kernel<LPR><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, X, e, lv, nd);
-  TAGREC_LAUNCH_CHECK();
-  if (g->n_long > 0) {
-    const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (e.row_mask) spmm_finish_noise_kernel<LPR, true><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
-    else spmm_finish_noise_kernel<LPR><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
-    TAGREC_LAUNCH_CHECK();
-  }
-  return TAGREC_OK;
+  const GraphView gv = view_of(g);
+  const bool masked = e.row_mask != nullptr;
+  return launch_with_long_rows(
+      g, LPR * 4,
+      [&](const LongView& lv) {
+        const unsigned grid = row_blocks(g->n_rows) + lv.chunk_blocks;
+        if (masked) spmm_rows_noise_kernel<LPR, true><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv, nd);
+        else spmm_rows_noise_kernel<LPR><<<grid, kVecThreads, 0, s>>>(gv, X, e, lv, nd);
+      },
+      [&] {
+        const unsigned fblocks = row_blocks(g->n_long);
+        if (masked) spmm_finish_noise_kernel<LPR, true><<<fblocks, kVecThreads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
+        else spmm_finish_noise_kernel<LPR><<<fblocks, kVecThreads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e, nd);
+      });
 }
 }  // namespace
 
@@ -1793,159 +1889,39 @@ extern "C" int tagrec_spmm_norm_acc_noise_f32(const tagrec_graph* g, const float
                                               int layer, int D, void* stream) {
   TAGREC_REQUIRE(g != nullptr && X != nullptr && Y_raw != nullptr && inv_norm != nullptr, "spmm_norm_acc_noise: null pointer");
   TAGREC_REQUIRE(static_cast<const void*>(X) != static_cast<const void*>(Y_raw), "spmm_norm_acc_noise: output aliases the gathered input");
-  int rc = noise_args("spmm_norm_acc_noise", eps, view, layer, D);
-  if (rc != TAGREC_OK) return rc;
+  TAGREC_TRY(noise_args("spmm_norm_acc_noise", eps, view, layer, D));
   if (!(aligned16(X) && aligned16(Y_raw) && (!acc || aligned16(acc))))
     return fail(TAGREC_E_UNSUPPORTED, "spmm_norm_acc_noise: the vector kernels need 16-byte aligned rows");
   if (g->n_rows == 0) return TAGREC_OK;
-  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{0.f, 0}, nullptr, nullptr, nullptr, row_mask, nullptr};
+  const EpiArgs e = norm_acc_epi(Y_raw, inv_norm, acc, acc_scale, DropMask{0.f, 0}, row_mask);
   const NoiseDir nd{eps, noise_key(seed, view, layer)};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (D) {
-    case 8: return launch_vec_noise<2>(g, X, e, nd, s);
-    case 16: return launch_vec_noise<4>(g, X, e, nd, s);
-    case 32: return launch_vec_noise<8>(g, X, e, nd, s);
-    case 64: return launch_vec_noise<16>(g, X, e, nd, s);
-    case 128: return launch_vec_noise<32>(g, X, e, nd, s);
-    default: return launch_vec_noise<64>(g, X, e, nd, s);
-  }
+  return vec_width_dispatch(D, "spmm_norm_acc_noise", [&](auto lc) { return launch_vec_noise<decltype(lc)::value>(g, X, e, nd, s); });
 }
 
 extern "C" int tagrec_noise_dir_f32(float* out, const int64_t* node_ids, int64_t n_rows, uint64_t seed, int view, int layer, int D,
                                     void* stream) {
   TAGREC_REQUIRE(n_rows >= 0 && (n_rows == 0 || out != nullptr), "noise_dir: null output or negative row count");
-  int rc = noise_args("noise_dir", 0.f, view, layer, D);
-  if (rc != TAGREC_OK) return rc;
+  TAGREC_TRY(noise_args("noise_dir", 0.f, view, layer, D));
   TAGREC_REQUIRE(aligned16(out), "noise_dir: out must be 16-byte aligned");
   if (n_rows == 0) return TAGREC_OK;
   const uint64_t key = noise_key(seed, view, layer);
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define NOISE_DIR(L)                                                                                              \
-  noise_dir_kernel<L><<<static_cast<unsigned>((n_rows + kWavesPerBlock * (kWave / L) - 1) / (kWavesPerBlock * (kWave / L))), \
-                        kWavesPerBlock * kWave, 0, s>>>(out, node_ids, n_rows, key);                              \
-  break
-  switch (D) {
-    case 8: NOISE_DIR(2);
-    case 16: NOISE_DIR(4);
-    case 32: NOISE_DIR(8);
-    case 64: NOISE_DIR(16);
-    case 128: NOISE_DIR(32);
-    default: NOISE_DIR(64);
-  }
-#undef NOISE_DIR
-  TAGREC_LAUNCH_CHECK();
-  return TAGREC_OK;
+  return vec_width_dispatch(D, "noise_dir", [&](auto lc) {
+    constexpr int LPR = decltype(lc)::value;
+    noise_dir_kernel<LPR><<<row_blocks(n_rows, kWavesPerBlock * (kWave / LPR)), kVecThreads, 0, s>>>(out, node_ids, n_rows, key);
+    TAGREC_LAUNCH_CHECK();
+    return TAGREC_OK;
+  });
 }
-
-// ---- edge dropout inside the products (`node_drop`, /root/reference/model/help/adj.py:170-191; EdgeDrop in common.h) -------
-// The `_edrop` form of a product multiplies by the matrix whose entry (i, j) is dropped with probability ed_p under ed_seed and
-// otherwise scaled by 1 / (1 - ed_p); ed_transposed != 0: the handle holds the transpose of the matrix the mask is defined on.
-namespace {
-int edrop_args(const char* who, float ed_p, int D) {
-  TAGREC_REQUIRE(ed_p >= 0.f && ed_p < 1.f, std::string(who) + ": edge-drop p must be in [0, 1)");
-  if (!(D == 8 || D == 16 || D == 32 || D == 64 || D == 128 || D == 256))
-    return fail(TAGREC_E_UNSUPPORTED, std::string(who) + ": edge dropout needs a vector-kernel width (D must be 8 .. 256, a power of two)");
-  return TAGREC_OK;
-}
-}  // namespace
 
 extern "C" int tagrec_edge_drop_mask_u8(const tagrec_graph* g, float p, uint64_t seed, int transposed, uint8_t* mask_out,
                                         void* stream) {
   TAGREC_REQUIRE(g != nullptr && (g->nnz == 0 || mask_out != nullptr), "edge_drop_mask: null pointer");
   TAGREC_REQUIRE(p >= 0.f && p < 1.f, "edge_drop_mask: p must be in [0, 1)");
   if (g->n_rows == 0 || g->nnz == 0) return TAGREC_OK;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  edge_drop_mask_kernel<<<blocks, kWavesPerBlock * kWave, 0, static_cast<hipStream_t>(stream)>>>(gv, EdgeDrop{p, seed, transposed != 0},
-                                                                                                mask_out);
-  TAGREC_LAUNCH_CHECK();
-  return TAGREC_OK;
-}
-
-extern "C" int tagrec_spmm_edrop_f32(const tagrec_graph* g, const float* X, float* Y, float ed_p, uint64_t ed_seed,
-                                     int ed_transposed, int D, void* stream) {
-  int rc = edrop_args("spmm_edrop", ed_p, D);
-  if (rc != TAGREC_OK) return rc;
-  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
-  EpiArgs e{Y, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr};
-  return launch_spmm<EPI_NONE>(g, X, e, D, stream, "spmm_edrop", &ed);
-}
-
-extern "C" int tagrec_spmm_norm_acc_rows_edrop_f32(const tagrec_graph* g, const float* X, float* Y_raw, float* inv_norm,
-                                                   float* acc, float acc_scale, const uint8_t* row_mask, float drop_p,
-                                                   uint64_t seed, float ed_p, uint64_t ed_seed, int ed_transposed, int D,
-                                                   void* stream) {
-  TAGREC_REQUIRE(inv_norm != nullptr, "spmm_norm_acc_rows_edrop: null inv_norm");
-  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_norm_acc_rows_edrop: p must be in [0, 1)");
-  int rc = edrop_args("spmm_norm_acc_rows_edrop", ed_p, D);
-  if (rc != TAGREC_OK) return rc;
-  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
-  EpiArgs e{Y_raw, inv_norm, acc, nullptr, nullptr, nullptr, acc_scale, DropMask{drop_p, seed}, nullptr, nullptr, nullptr, row_mask, nullptr};
-  return launch_spmm<EPI_NORM_ACC>(g, X, e, D, stream, "spmm_norm_acc_rows_edrop", &ed);
-}
-
-extern "C" int tagrec_spmm_normbwd_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
-                                                    const unsigned* in_count, const float* X_raw, const float* inv_norm,
-                                                    const float* dZ, float d_scale, float drop_p, uint64_t seed, float* G_out,
-                                                    uint8_t* out_flags, unsigned* out_count, const uint8_t* row_mask,
-                                                    const uint8_t* dz_flags, float ed_p, uint64_t ed_seed, int ed_transposed,
-                                                    int D, void* stream) {
-  TAGREC_REQUIRE(X_raw != nullptr && inv_norm != nullptr && dZ != nullptr, "spmm_normbwd_sparse_edrop: null X_raw, inv_norm or dZ");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_normbwd_sparse_edrop: in_count without in_flags");
-  TAGREC_REQUIRE((out_flags == nullptr) == (out_count == nullptr), "spmm_normbwd_sparse_edrop: out_flags and out_count go together");
-  TAGREC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "spmm_normbwd_sparse_edrop: p must be in [0, 1)");
-  int rc = edrop_args("spmm_normbwd_sparse_edrop", ed_p, D);
-  if (rc != TAGREC_OK) return rc;
-  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
-  EpiArgs e{G_out, const_cast<float*>(inv_norm), nullptr, X_raw, dZ, nullptr, d_scale, DropMask{drop_p, seed}, in_flags, in_count, out_flags, row_mask, dz_flags};
-  rc = launch_spmm<EPI_NORMBWD>(g, G_in, e, D, stream, "spmm_normbwd_sparse_edrop", &ed);
-  if (rc != TAGREC_OK || !out_flags) return rc;
-  return count_flags(out_flags, g->n_rows, out_count, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int tagrec_spmm_axpy_sparse_edrop_f32(const tagrec_graph* g, const float* G_in, const uint8_t* in_flags,
-                                                 const unsigned* in_count, const float* B, float b_scale, float* G_out,
-                                                 const uint8_t* row_mask, const uint8_t* b_flags, float ed_p, uint64_t ed_seed,
-                                                 int ed_transposed, int D, void* stream) {
-  TAGREC_REQUIRE(B != nullptr, "spmm_axpy_sparse_edrop: null B");
-  TAGREC_REQUIRE(in_flags != nullptr || in_count == nullptr, "spmm_axpy_sparse_edrop: in_count without in_flags");
-  int rc = edrop_args("spmm_axpy_sparse_edrop", ed_p, D);
-  if (rc != TAGREC_OK) return rc;
-  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
-  EpiArgs e{G_out, nullptr, nullptr, nullptr, B, nullptr, b_scale, DropMask{0.f, 0}, in_flags, in_count, nullptr, row_mask, b_flags};
-  return launch_spmm<EPI_AXPY>(g, G_in, e, D, stream, "spmm_axpy_sparse_edrop", &ed);
-}
-
-extern "C" int tagrec_spmm_listed_edrop_f32(const tagrec_graph* g, const int64_t* rows, int64_t n_listed, const float* X, float* Y,
-                                            int D, float* ws, int64_t ws_floats, float ed_p, uint64_t ed_seed, int ed_transposed,
-                                            void* stream) {
-  TAGREC_REQUIRE(g != nullptr && X != nullptr && Y != nullptr && (n_listed == 0 || rows != nullptr), "spmm_listed_edrop: null pointer");
-  TAGREC_REQUIRE(n_listed >= 0 && n_listed * kListedSplits < (1ll << 31), "spmm_listed_edrop: bad row count");
-  TAGREC_REQUIRE(aligned16(X) && aligned16(Y) && aligned16(ws), "spmm_listed_edrop: rows must be 16-byte aligned");
-  TAGREC_REQUIRE(n_listed == 0 || (ws != nullptr && ws_floats >= tagrec_spmm_listed_workspace(n_listed, D)),
-                 "spmm_listed_edrop: workspace smaller than tagrec_spmm_listed_workspace(n_listed, D)");
-  int rc = edrop_args("spmm_listed_edrop", ed_p, D);
-  if (rc != TAGREC_OK) return rc;
-  if (n_listed == 0) return TAGREC_OK;
-  const EdgeDrop ed{ed_p, ed_seed, ed_transposed != 0};
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned blocks = static_cast<unsigned>(n_listed * kListedSplits);
-  const int threads = kWavesPerBlock * kWave;
-#define LISTED(L)                                                                                   \
-  spmm_listed_edrop_kernel<L><<<blocks, threads, 0, s>>>(gv, rows, X, ws, ed);                      \
-  TAGREC_LAUNCH_CHECK();                                                                            \
-  spmm_listed_fold_kernel<L><<<static_cast<unsigned>((n_listed * L + 255) / 256), 256, 0, s>>>(ws, Y, n_listed); \
-  break
-  switch (D) {
-    case 8: LISTED(2);
-    case 16: LISTED(4);
-    case 32: LISTED(8);
-    case 64: LISTED(16);
-    case 128: LISTED(32);
-    default: LISTED(64);
-  }
-#undef LISTED
+  edge_drop_mask_kernel<<<row_blocks(g->n_rows), kVecThreads, 0, static_cast<hipStream_t>(stream)>>>(view_of(g), edge_drop(p, seed, transposed),
+                                                                                                    mask_out);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }
@@ -1955,48 +1931,32 @@ namespace {
 template <int LPR, int EPI>
 int launch_pull_da(const tagrec_graph* g, const int32_t* pair, const float* dOut, const float* Ej, float* da, const EpiArgs& e,
                    hipStream_t s) {
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const int threads = kWavesPerBlock * kWave;
-  constexpr int rows_per_block = kWavesPerBlock * (kWave / LPR);          // every lane group of a wave walks its own row
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + rows_per_block - 1) / rows_per_block);
-  LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
-  if (g->n_long > 0) {
-    int rc = ensure_slab(g, LPR * 4);
-    if (rc != TAGREC_OK) return rc;
-    lv.slab = g->slab;
-    lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-  }
-  attn_pull_da_kernel<LPR, EPI><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, pair, dOut, Ej, da, e, lv);
-  TAGREC_LAUNCH_CHECK();
-  if (g->n_long > 0) {
-    const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-    spmm_finish_kernel<LPR, EPI><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-    TAGREC_LAUNCH_CHECK();
-  }
-  return TAGREC_OK;
+  const GraphView gv = view_of(g);
+  return launch_with_long_rows(
+      g, LPR * 4,
+      [&](const LongView& lv) {
+        const unsigned blocks = row_blocks(g->n_rows, kWavesPerBlock * (kWave / LPR));   // every lane group of a wave walks its own row
+        attn_pull_da_kernel<LPR, EPI><<<blocks + lv.chunk_blocks, kVecThreads, 0, s>>>(gv, pair, dOut, Ej, da, e, lv);
+      },
+      [&] { launch_finish<LPR, EPI>(g, gv, e, s); });
 }
 
 template <int A, int EPI>
 int launch_pull_dq(const tagrec_graph* g, const float2* comp, const float* vv, const EpiArgs& e, hipStream_t s) {
-  constexpr int LPR = A / 4;
-  const GraphView gv{g->n_rows, g->rowptr, g->col, g->val, g->n_cols};
-  const int threads = kWavesPerBlock * kWave;
-  const unsigned blocks = static_cast<unsigned>((g->n_rows + kWavesPerBlock - 1) / kWavesPerBlock);
-  LongView lv{g->long_rows, g->chunk_desc, g->n_chunks, nullptr, 0};
-  if (g->n_long > 0) {
-    int rc = ensure_slab(g, A);
-    if (rc != TAGREC_OK) return rc;
-    lv.slab = g->slab;
-    lv.chunk_blocks = static_cast<unsigned>((g->n_chunks + kWavesPerBlock - 1) / kWavesPerBlock);
-  }
-  attn_pull_dq_kernel<A, EPI><<<blocks + lv.chunk_blocks, threads, 0, s>>>(gv, comp, vv, e, lv);
-  TAGREC_LAUNCH_CHECK();
-  if (g->n_long > 0) {
-    const unsigned fblocks = static_cast<unsigned>((g->n_long + kWavesPerBlock - 1) / kWavesPerBlock);
-    spmm_finish_kernel<LPR, EPI><<<fblocks, threads, 0, s>>>(gv, g->long_rows, g->long_base, g->n_long, g->slab, e);
-    TAGREC_LAUNCH_CHECK();
-  }
-  return TAGREC_OK;
+  const GraphView gv = view_of(g);
+  return launch_with_long_rows(
+      g, A,
+      [&](const LongView& lv) {
+        attn_pull_dq_kernel<A, EPI><<<row_blocks(g->n_rows) + lv.chunk_blocks, kVecThreads, 0, s>>>(gv, comp, vv, e, lv);
+      },
+      [&] { launch_finish<A / 4, EPI>(g, gv, e, s); });
+}
+
+// the epilogue of both pulls: the pulled rows, plus B when there is one
+EpiArgs pull_epi(float* out, const float* B) {
+  EpiArgs e;
+  e.Y = out; e.B = B; e.s = 1.0f;
+  return e;
 }
 }  // namespace
 
@@ -2006,19 +1966,17 @@ extern "C" int tagrec_attn_pull_da_f32(const tagrec_graph* g, const int32_t* pai
   if (g->n_rows == 0) return TAGREC_OK;
   TAGREC_REQUIRE(Ej && dEj && (g->nnz == 0 || (dOut && pair && da)), "attn_pull_da: null pointer");
   TAGREC_REQUIRE(aligned16(dOut) && aligned16(Ej) && aligned16(dEj) && (!B || aligned16(B)), "attn_pull_da: rows must be 16-byte aligned");
+  if (!is_vec_width(D) || D < 16) return fail(TAGREC_E_UNSUPPORTED, "attn_pull_da: D must be 16, 32, 64, 128 or 256");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  EpiArgs e{dEj, nullptr, nullptr, nullptr, B, nullptr, 1.0f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr, nullptr};
-#define PULL(L) (B ? launch_pull_da<L, EPI_AXPY>(g, pair, dOut, Ej, da, e, s) : launch_pull_da<L, EPI_NONE>(g, pair, dOut, Ej, da, e, s))
-  switch (D) {
-    case 16: return PULL(4);
-    case 32: return PULL(8);
-    case 64: return PULL(16);
-    case 128: return PULL(32);
-    case 256: return PULL(64);
-    default: break;
-  }
-#undef PULL
-  return fail(TAGREC_E_UNSUPPORTED, "attn_pull_da: D must be 16, 32, 64, 128 or 256");
+  const EpiArgs e = pull_epi(dEj, B);
+  return vec_width_dispatch(D, "attn_pull_da", [&](auto lc) {
+    constexpr int LPR = decltype(lc)::value;
+    if constexpr (LPR >= 4) {
+      return B ? launch_pull_da<LPR, EPI_AXPY>(g, pair, dOut, Ej, da, e, s) : launch_pull_da<LPR, EPI_NONE>(g, pair, dOut, Ej, da, e, s);
+    } else {
+      return static_cast<int>(TAGREC_E_UNSUPPORTED);      // D = 8: refused above, and no kernel is built for it
+    }
+  });
 }
 
 extern "C" int tagrec_attn_pull_dq_f32(const tagrec_graph* g, const float* comp, const float* v, int A, const float* B, float* dQ,
@@ -2028,14 +1986,14 @@ extern "C" int tagrec_attn_pull_dq_f32(const tagrec_graph* g, const float* comp,
   TAGREC_REQUIRE(v && dQ && (g->nnz == 0 || comp), "attn_pull_dq: null pointer");
   TAGREC_REQUIRE(aligned16(dQ) && (!B || aligned16(B)) && (reinterpret_cast<uintptr_t>(comp) & 7u) == 0, "attn_pull_dq: misaligned buffer");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  EpiArgs e{dQ, nullptr, nullptr, nullptr, B, nullptr, 1.0f, DropMask{0.f, 0}, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const EpiArgs e = pull_epi(dQ, B);
   const float2* c2 = reinterpret_cast<const float2*>(comp);
-#define PULL(AA) (B ? launch_pull_dq<AA, EPI_AXPY>(g, c2, v, e, s) : launch_pull_dq<AA, EPI_NONE>(g, c2, v, e, s))
-  switch (A) {
-    case 16: return PULL(16);
-    case 32: return PULL(32);
-    default: break;
-  }
-#undef PULL
+  auto pull = [&](auto ac) {
+    constexpr int AA = decltype(ac)::value;
+    return B ? launch_pull_dq<AA, EPI_AXPY>(g, c2, v, e, s) : launch_pull_dq<AA, EPI_NONE>(g, c2, v, e, s);
+  };
+  if (A == 16) return pull(std::integral_constant<int, 16>{});
+  if (A == 32) return pull(std::integral_constant<int, 32>{});
   return fail(TAGREC_E_UNSUPPORTED, "attn_pull_dq: A must be 16 or 32 (the relu bits of a pair travel in one 32-bit word)");
 }
+

@@ -703,6 +703,26 @@ def test_adam_folded_into_the_last_hop(square, D, flagged, step, form):
     print(f"[spmm] adam hop D={D} flagged={flagged} step={step} {form}: bit-identical to product + rowops Adam")
 
 
+def test_a_refused_adam_hop_leaves_the_device_step_counter_alone():
+    """The capturable form advances the device step counter only after every host-side check of the product has passed: a
+    null graph handle (8 rows, D = 8, everything else valid) is refused as an invalid argument, the counter still reads 5
+    and the factors, the parameters and the moments are untouched.  No product kernel is launched."""
+    n, D = 8, 8
+    Gg, bg = R.randn(n, D, seed=1).to(DEV), R.randn(n, D, seed=2).to(DEV)
+    p0, m0, v0 = R.randn(n, D, seed=3).to(DEV), R.randn(n, D, seed=4, scale=0.01).to(DEV), R.randn(n, D, seed=5, scale=0.01).abs().to(DEV)
+    p, m, v = p0.clone(), m0.clone(), v0.clone()
+    step_dev = torch.full((1,), 5, dtype=torch.int64, device=DEV)
+    coef0 = torch.tensor([0.25, 0.75], dtype=torch.float32, device=DEV)
+    coef = coef0.clone()
+    rc = _lib.load().tagrec_spmm_axpy_adam_graph_f32(None, Gg, None, None, bg, S, None, p, m, v, 0.01, 0.9, 0.999, 1e-8, step_dev, coef,
+                                                     D, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == -1                                                      # TAGREC_E_INVALID
+    assert "null graph handle" in _lib.load().tagrec_last_error().decode()
+    assert int(step_dev) == 5 and same_bits(coef, coef0)
+    assert same_bits(p, p0) and same_bits(m, m0) and same_bits(v, v0)
+
+
 # ========================================================================================================== listed rows
 def _listed_rows(lad, keys):
     rows = list(range(lad.n_rows)) + [lad.special[k] for k in keys]

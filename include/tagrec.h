@@ -394,6 +394,64 @@ int tagrec_rank_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
                         int64_t B, int K, const float* coef, const float* g,
                         float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
 
+/* ---- Weighted pointwise binary cross-entropy on COMPACT rows (UltraGCN; csrc/rowops.hip) ----
+ * The slot layout of the rank kernels with S = 1 + K + M slots per tuple: Ub [B, D], Ib [S B, D], slot j of tuple b at row
+ * j B + b; j = 0 the positive, 1 .. K the negatives, K + 1 .. K + M the positive's co-occurrence neighbours.  K >= 1,
+ * M >= 0, S <= 4096 (the kernels loop over the slots).  Labels t_j = +1 for j = 0 and j > K, -1 for the negatives;
+ * weight [B, S] (contiguous, >= 0).  With s_bj = Ub[b] . Ib[j B + b] and softplus(x) = max(x, 0) + log1p(exp(-|x|)):
+ *   loss_out[0] = (1 / B) sum_b sum_j weight[b, j] softplus(-t_j s_bj)
+ *   loss_out[1] = 0.5 (|Ureg[b]|^2 + sum_{j <= K} |Ireg[j B + b]|^2) / B summed over b (the neighbour slots carry no L2)
+ *   coef [B, S] = -t_j weight[b, j] sigmoid(-t_j s_bj) / B         (1 / B folded in; a zero weight gives an exact zero)
+ * `partials`: scratch of 2*ceil(B/4) floats; the two-stage reduction is deterministic. */
+int tagrec_wbce_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                        int64_t B, int K, int M, const float* weight,
+                        float* coef, float* partials, float* loss_out, void* stream);
+/* bwd STORES (no atomics, no read of the old contents) every row of
+ *   dUb[b]       = g0 * sum_j coef[b, j] * Ib[j B + b]     (ascending j)
+ *   dIb[j B + b] = g0 * coef[b, j] * Ub[b]
+ *   dUreg[b] = g1 / B * Ureg[b];  dIreg[j B + b] = g1 / B * Ireg[j B + b] for j <= K and 0 for the neighbour slots
+ * g, the NULL forms and the shared-buffer form (dUreg = dUb, dIreg = dIb with Ureg = Ub, Ireg = Ib) as in tagrec_rank_bwd_f32. */
+int tagrec_wbce_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D,
+                        const float* Ureg, const float* Ireg, int64_t ldreg, int Dreg,
+                        int64_t B, int K, int M, const float* coef, const float* g,
+                        float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream);
+
+/* ---- Item co-occurrence top-k: the k heaviest columns of every row of the sparse A^T A (csrc/cooc.hip) ----
+ * A = the 0 / 1 user x item train matrix, given as two CSRs with sorted, duplicate-free rows: item -> users (iu_ptr
+ * [n_item + 1], iu_idx) and user -> items (ui_ptr [n_user + 1], ui_idx); every id must lie inside its range (not checked on
+ * the device).  c_ij = |N(i) n N(j)|, c_ii = deg(i), D_i = sum_j c_ij; zero_diagonal: c_ii counts as 0.
+ *   tagrec_cooc_degree_i64     D [n_item] = sum_{u in N(i)} deg(u) [- deg(i)]
+ *   tagrec_cooc_topk_*_f32     for every listed item i (items [n_listed], int32, no repeats): row i of nbr_id / nbr_w
+ *                              [n_item, k] = the first k candidates j (c_ij > 0) in descending fp64 c_ij^2 / (D_j + 1), ties to
+ *                              the lower id, padded with -1 / 0;  nbr_w = (float)(c_ij sqrt(D_i + 1) / D_i / sqrt(D_j + 1)),
+ *                              formed in fp64.  1 <= k <= 64.  Rows of items that are not listed are not touched.
+ * Counts are summed with integer atomics only: the outputs do not depend on the execution order.
+ *   light: one block per listed item, counts in an LDS hash table; every listed item needs D_i <= tagrec_cooc_lds_limit()
+ *          (an item above it gets an all-pad row).
+ *   heavy: any D_i; `workspace` = rows x n_item int32, ALL ZERO on entry and all zero again on return; min(rows, n_listed,
+ *          tagrec_cooc_max_rows()) blocks each own one counter row and take the listed items in turn.
+ *   hub:   a listed item's walk cut into n_part parts (part p: hub part_hub[p], users iu_idx[part_u0[p] .. part_u1[p]); the parts of
+ *          hub h are hub_part_ptr[h] .. hub_part_ptr[h + 1], contiguous, and cover its user list exactly once), one block per part;
+ *          `workspace` = n_hub x n_item int32, all zero on entry and on return; part_id / part_c: scratch of n_part x k int32.
+ *          Three launches: every part adds into its hub's row, every part exchanges and keeps its k best, one block per hub merges. */
+int tagrec_cooc_lds_limit(void);
+int tagrec_cooc_max_rows(void);
+int tagrec_cooc_topk_hub_f32(const int64_t* iu_ptr, const int32_t* iu_idx, const int64_t* ui_ptr, const int32_t* ui_idx,
+                             const int64_t* D, const int32_t* hub_items, int64_t n_hub, const int32_t* part_hub,
+                             const int64_t* part_u0, const int64_t* part_u1, int64_t n_part, const int64_t* hub_part_ptr,
+                             int64_t n_item, int k, int zero_diagonal, int32_t* workspace, int32_t* part_id,
+                             int32_t* part_c, int32_t* nbr_id, float* nbr_w, void* stream);
+int tagrec_cooc_degree_i64(const int64_t* iu_ptr, const int32_t* iu_idx, const int64_t* ui_ptr, int64_t n_item,
+                           int zero_diagonal, int64_t* D, void* stream);
+int tagrec_cooc_topk_light_f32(const int64_t* iu_ptr, const int32_t* iu_idx, const int64_t* ui_ptr, const int32_t* ui_idx,
+                               const int64_t* D, const int32_t* items, int64_t n_listed, int64_t n_item, int k,
+                               int zero_diagonal, int32_t* nbr_id, float* nbr_w, void* stream);
+int tagrec_cooc_topk_heavy_f32(const int64_t* iu_ptr, const int32_t* iu_idx, const int64_t* ui_ptr, const int32_t* ui_idx,
+                               const int64_t* D, const int32_t* items, int64_t n_listed, int64_t n_item, int k,
+                               int zero_diagonal, int32_t* workspace, int64_t rows, int32_t* nbr_id, float* nbr_w,
+                               void* stream);
+
 /* ---- In-batch sampled softmax on COMPACT rows: a fused B x B loss, the score matrix is never stored (csrc/inbatch.hip) ----
  * Ub [B, D] and Ib [B, D] (row stride ld floats): row b of Ib is the positive of row b of Ub, and every other row of Ib is
  * a negative of it.  The kernels do not know what the two operands stand for (users / items, or two views of one node set).

@@ -13,6 +13,8 @@ Reference name                      here
   -- (not in the reference)           tagrec_amd.SimGCL: LightGCN + contrastive noise views (get_config("simgcl"))
   -- (not in the reference)           tagrec_amd.DirectAU: LightGCN under the alignment / uniformity loss (get_config("directau"))
   -- (not in the reference)           tagrec_amd.NCL: LightGCN + structure / prototype contrast (get_config("ncl"))
+  -- (not in the reference)           tagrec_amd.UltraGCN: plain tables under a weighted pointwise BCE (get_config("ultragcn"))
+  -- (not in the reference)           tagrec_amd.item_cooccurrence_topk: top-k of the sparse item-item product (cooc.py)
   -- (not in the reference)           tagrec_amd.kmeans: Lloyd's algorithm on the device (kmeans.py)
   train_data.BPR_training_data        tagrec_amd.BPR_training_data
   training.Basic_train / Basic_test   tagrec_amd.Basic_train / Basic_test
@@ -31,6 +33,8 @@ from .simgcl import SimGCL  # noqa: F401
 from .directau import DirectAU  # noqa: F401
 from .kmeans import kmeans  # noqa: F401
 from .ncl import NCL  # noqa: F401
+from .cooc import item_cooccurrence_topk  # noqa: F401
+from .ultragcn import UltraGCN  # noqa: F401
 from .ngcf import NGCF  # noqa: F401
 from .tgcn import TGCN  # noqa: F401
 from .dgcf import DGCF  # noqa: F401

@@ -38,6 +38,16 @@ def refuse_deterministic(config, model, not_covered):
         raise TagrecError(f"{model}: deterministic=True is not covered (only the LightGCN and NGCF steps are): {not_covered}")
 
 
+def refuse_ultragcn(config, what):
+    """Every model but UltraGCN refuses the ug_* keys (and the "ultragcn" configuration) instead of ignoring them."""
+    if config.get("model") == "ultragcn":
+        raise TagrecError(f"{what}: the \"ultragcn\" configuration is not covered (weighted pointwise BCE on plain tables: "
+                          "tagrec_amd.UltraGCN and BPR_training_data only)")
+    keys = sorted(k for k in config if isinstance(k, str) and k.startswith("ug_"))
+    if keys:
+        raise TagrecError(f"{what}: {', '.join(keys)} belong to UltraGCN (get_config(\"ultragcn\")); this model does not read them")
+
+
 def refuse_multi_negative(config, what):
     """Models and producers that consume (user, positive, one negative) triplets refuse n_negatives != 1, the "softmax"
     loss and negatives="in_batch" loudly instead of training on the first negative (only the LightGCN and NGCF steps and

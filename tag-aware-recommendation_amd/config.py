@@ -75,8 +75,15 @@ _PER_MODEL = {
     "ncl": {"mul_loss_func": "softplus", "norm_type": "bi_norm", "cor_batch": 100, "use_tag": False,
             "ncl_struct_rate": 5e-4, "ncl_proto_rate": 3e-4, "ncl_alpha": 1.0, "ncl_temperature": 0.1,
             "ncl_clusters": 1000, "ncl_kmeans_iters": 20, "ncl_warm_up": 20},
+    # UltraGCN (not in the reference; Mao et al., CIKM 2021): no propagation -- plain user / item tables under a degree-weighted
+    # pointwise BCE plus a constraint that pulls a user towards the ug_neighbors items that co-occur most with the positive
+    # (ultragcn.py, cooc.py, rowops.wbce_*).  The terms are MEANS over the batch; the defaults are untuned and no accuracy run exists
+    "ultragcn": {"mul_loss_func": "softplus", "use_tag": False, "n_negatives": 16,
+                 "ug_w": (1e-6, 1.0, 1e-6, 1.0), "ug_negative_weight": 10.0, "ug_lambda": 1.0, "ug_neighbors": 10,
+                 "ug_zero_diagonal": False},
 }
 MAX_AU_T = 20.0                   # a term of the uniformity sum is >= e^(-4 au_t): e^-80 is still a normal fp32 number
+MAX_UG_NEIGHBORS = 64             # cooc.item_cooccurrence_topk keeps at most 64 neighbours per item
 
 
 def get_config(model="lightgcn", **overrides):
@@ -98,6 +105,11 @@ def get_config(model="lightgcn", **overrides):
         check_alignment(cfg)
     if model == "ncl":
         check_ncl(cfg)
+    if model == "ultragcn":
+        check_ultragcn(cfg)
+    else:
+        from ._lib import refuse_ultragcn
+        refuse_ultragcn(cfg, f"get_config({model!r})")
     return cfg
 
 
@@ -224,6 +236,34 @@ def check_ncl(cfg):
             raise TagrecError(f"{name} must be an integer >= {low}, got {v!r}")
     return (float(vals["ncl_struct_rate"]), float(vals["ncl_proto_rate"]), float(vals["ncl_alpha"]), float(tau),
             vals["ncl_clusters"], vals["ncl_kmeans_iters"], vals["ncl_warm_up"])
+
+
+def check_ultragcn(cfg):
+    """The five UltraGCN keys of a config -> (w1 .. w4, negative_weight, lambda, neighbors, zero_diagonal); a bad value is
+    refused: the weights finite and >= 0, ug_neighbors an integer in 0 .. 64 (0: no neighbour term), ug_zero_diagonal a bool.
+    The objective is its own: negatives="in_batch", softmax_over="catalogue" and mul_loss_func="softmax" are refused."""
+    from ._lib import TagrecError
+    d = _PER_MODEL["ultragcn"]
+    w = cfg.get("ug_w", d["ug_w"])
+    if not isinstance(w, (tuple, list)) or len(w) != 4:
+        raise TagrecError(f"ug_w must be four numbers (w1, w2, w3, w4), got {w!r}")
+    nums = [(f"ug_w[{i}]", v) for i, v in enumerate(w)] + [(k, cfg.get(k, d[k])) for k in ("ug_negative_weight", "ug_lambda")]
+    for name, v in nums:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf"):
+            raise TagrecError(f"{name} must be a finite number >= 0, got {v!r}")
+    m, zd = cfg.get("ug_neighbors", d["ug_neighbors"]), cfg.get("ug_zero_diagonal", d["ug_zero_diagonal"])
+    if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= MAX_UG_NEIGHBORS:
+        raise TagrecError(f"ug_neighbors must be an integer in 0 .. {MAX_UG_NEIGHBORS}, got {m!r}")
+    if not isinstance(zd, bool):
+        raise TagrecError(f"ug_zero_diagonal must be True or False, got {zd!r}")
+    if cfg.get("negatives", "sampled") != "sampled":
+        raise TagrecError(f"ultragcn scores sampled negatives one by one: it needs negatives=\"sampled\", got {cfg.get('negatives')!r}")
+    if cfg.get("softmax_over", "negatives") != "negatives":
+        raise TagrecError("ultragcn is a pointwise loss, there is no softmax: it needs softmax_over=\"negatives\" (the default, "
+                          f"unused), got {cfg.get('softmax_over')!r}")
+    if cfg.get("mul_loss_func", "softplus") == "softmax":
+        raise TagrecError("ultragcn is a pointwise loss: mul_loss_func=\"softmax\" is not covered")
+    return tuple(float(v) for v in w), float(nums[4][1]), float(nums[5][1]), m, zd
 
 
 CFG =get_config("lightgcn")

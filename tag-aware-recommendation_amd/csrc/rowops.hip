@@ -537,6 +537,106 @@ __global__ __launch_bounds__(kThreads) void rank_bwd_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// Weighted pointwise binary cross-entropy on COMPACT rows (UltraGCN, Mao et al., CIKM 2021), in the slot layout of the rank
+// kernels: tuple b = (user row b of Ub, item rows j B + b of Ib), S = 1 + K + M slots, j = 0 the positive (label t = +1),
+// 1 .. K the negatives (t = -1), K + 1 .. K + M the positive's co-occurrence neighbours (t = +1).  Every slot is scored on its
+// own: loss_b = sum_j w_bj softplus(-t_j s_bj), coef[b, j] = d (loss_b / B) / d s_bj = -t_j w_bj sigmoid(-t_j s_bj) / B.  One
+// wave per tuple LOOPS over the slots, so S is not bound by the wave width.  The L2 part reads the user row and slots 0 .. K
+// (the neighbour slots carry none).  A tuple's loss and L2 sums are kept in fp64 and rounded once, into the block's partial.
+__device__ __forceinline__ float softplus_stable(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+
+__global__ __launch_bounds__(kThreads) void wbce_fwd_kernel(const float* __restrict__ Ub, const float* __restrict__ Ib,
+                                                            int64_t ld, int D, const float* __restrict__ Ur,
+                                                            const float* __restrict__ Ir, int64_t ldr, int Dr, int64_t B,
+                                                            int K, int S, const float* __restrict__ weight, float inv_b,
+                                                            float* __restrict__ coef, float* __restrict__ partials) {
+  __shared__ double sh[2][kThreads / kWave];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int w = threadIdx.x >> 6;
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + w;
+  double loss = 0.0, reg = 0.0;
+  if (b < B) {
+    const float* ur = Ub + b * ld;
+    float uh[kRankHeld];
+#pragma unroll
+    for (int t = 0; t < kRankHeld; ++t) uh[t] = lane + t * kWave < D ? ur[lane + t * kWave] : 0.f;
+    float c = 0.f;                                    // coefficient of slot j0 + lane of the current run of 64 slots
+    for (int j = 0; j < S; ++j) {
+      const float* ir = Ib + (static_cast<int64_t>(j) * B + b) * ld;
+      float d = 0.f;
+#pragma unroll
+      for (int t = 0; t < kRankHeld; ++t)
+        if (lane + t * kWave < D) d = fmaf(uh[t], ir[lane + t * kWave], d);
+      for (int k = lane + kRankHeld * kWave; k < D; k += kWave) d = fmaf(ur[k], ir[k], d);
+      d = wave_sum(d);                                // (the butterfly leaves the sum in every lane)
+      const float t = (j == 0 || j > K) ? 1.f : -1.f;
+      const float x = -t * d;
+      const float wt = weight[b * S + j];
+      loss += static_cast<double>(wt * softplus_stable(x));
+      if (lane == (j & (kWave - 1))) c = -t * wt * (1.f / (1.f + expf(-x))) * inv_b;
+      if ((j & (kWave - 1)) == kWave - 1 || j == S - 1) {
+        const int at = (j & ~(kWave - 1)) + lane;
+        if (at <= j) coef[b * S + at] = c;
+      }
+    }
+    if (Ur) {
+      for (int j = -1; j <= K; ++j) {                 // -1: the user row
+        const float* r = j < 0 ? Ur + b * ldr : Ir + (static_cast<int64_t>(j) * B + b) * ldr;
+        float ss = 0.f;
+        for (int k = lane; k < Dr; k += kWave) ss = fmaf(r[k], r[k], ss);
+        reg += static_cast<double>(wave_sum(ss));
+      }
+      reg *= 0.5;
+    }
+  }
+  if (lane == 0) { sh[0][w] = loss; sh[1][w] = reg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double l = 0.0, g = 0.0;
+    for (int i = 0; i < kThreads / kWave; ++i) { l += sh[0][i]; g += sh[1][i]; }
+    partials[2 * blockIdx.x] = static_cast<float>(l);
+    partials[2 * blockIdx.x + 1] = static_cast<float>(g);
+  }
+}
+
+// Backward: lanes map to consecutive columns; every output row is written exactly once with plain stores (the L2 rows of the
+// neighbour slots with zeros).  `shared` as in rank_bwd_kernel; coef already carries 1 / B.
+__global__ __launch_bounds__(kThreads) void wbce_bwd_kernel(const float* __restrict__ Ub, const float* __restrict__ Ib,
+                                                            int64_t ld, int D, const float* __restrict__ Ur,
+                                                            const float* __restrict__ Ir, int64_t ldr, int Dr, int64_t B,
+                                                            int K, int S, const float* __restrict__ coef,
+                                                            const float* __restrict__ g, float inv_b, float* dU, float* dI,
+                                                            float* dUr, float* dIr) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t b = static_cast<int64_t>(blockIdx.x) * (kThreads / kWave) + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float g0 = g ? g[0] : 1.f;
+  const float cr = (g ? g[1] : 1.f) * inv_b;
+  const bool shared = Ur != nullptr && dU != nullptr && dUr == dU;
+  if (dU) {
+    for (int k = lane; k < D; k += kWave) {
+      const float uv = Ub[b * ld + k];
+      float du = 0.f;
+      for (int j = 0; j < S; ++j) {
+        const float c = g0 * coef[b * S + j];
+        const int64_t at = (static_cast<int64_t>(j) * B + b) * ld + k;
+        const float iv = Ib[at];
+        du = fmaf(c, iv, du);
+        dI[at] = (shared && j <= K) ? fmaf(cr, iv, c * uv) : c * uv;
+      }
+      dU[b * ld + k] = shared ? fmaf(cr, uv, du) : du;
+    }
+  }
+  if (Ur && !shared) {
+    for (int k = lane; k < Dr; k += kWave) dUr[b * ldr + k] = cr * Ur[b * ldr + k];
+    for (int j = 0; j < S; ++j) {
+      const int64_t at = (static_cast<int64_t>(j) * B + b) * ldr;
+      for (int k = lane; k < Dr; k += kWave) dIr[at + k] = j <= K ? cr * Ir[at + k] : 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Negative sampler (train_data/utils.py:19-28 `sample_neg_item`, :31-40 `sample_neg_tail`): one uniform draw in
 // [0, n_right) per positive row, re-drawn while (left id, draw) is a positive pair.  The positives of a left id are
 // the sorted row `cols[rowptr[l] .. rowptr[l+1])`, so membership is a binary search in that row.  Counter-based
@@ -867,6 +967,50 @@ extern "C" int tagrec_rank_bwd_f32(const float* Ub, const float* Ib, int64_t ld,
   const int64_t blocks = (B + 3) / 4;
   rank_bwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, static_cast<hipStream_t>(stream)>>>(
       Ub, Ib, ld, D, Ureg, Ireg, ldreg, Dreg, B, K, coef, g, 1.0f / static_cast<float>(B), dUb, dIb, dUreg, dIreg);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+static int wbce_shape(const char* what, int64_t B, int D, int64_t ld, int K, int M) {
+  TAGREC_REQUIRE(B >= 1 && D >= 1 && ld >= D, std::string(what) + ": bad shape");
+  TAGREC_REQUIRE(K >= 1 && M >= 0 && static_cast<int64_t>(1) + K + M <= 4096,
+                 std::string(what) + ": K >= 1, M >= 0 and 1 + K + M <= 4096 slots expected");
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_wbce_fwd_f32(const float* Ub, const float* Ib, int64_t ld, int D, const float* Ureg, const float* Ireg,
+                                   int64_t ldreg, int Dreg, int64_t B, int K, int M, const float* weight, float* coef,
+                                   float* partials, float* loss_out, void* stream) {
+  TAGREC_REQUIRE(Ub && Ib && weight && coef && partials && loss_out, "wbce_fwd: null pointer");
+  TAGREC_TRY(wbce_shape("wbce_fwd", B, D, ld, K, M));
+  TAGREC_REQUIRE((Ureg == nullptr) == (Ireg == nullptr), "wbce_fwd: Ureg/Ireg must both be given or both null");
+  TAGREC_REQUIRE(!Ureg || (Dreg >= 1 && ldreg >= Dreg), "wbce_fwd: bad reg shape");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t blocks = (B + 3) / 4;
+  const float inv_b = 1.0f / static_cast<float>(B);
+  wbce_fwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, s>>>(Ub, Ib, ld, D, Ureg, Ireg, ldreg, Dreg, B, K, 1 + K + M,
+                                                                      weight, inv_b, coef, partials);
+  TAGREC_LAUNCH_CHECK();
+  bpr_reduce_kernel<<<1, kThreads, 0, s>>>(partials, blocks, inv_b, loss_out);
+  TAGREC_LAUNCH_CHECK();
+  return TAGREC_OK;
+}
+
+extern "C" int tagrec_wbce_bwd_f32(const float* Ub, const float* Ib, int64_t ld, int D, const float* Ureg, const float* Ireg,
+                                   int64_t ldreg, int Dreg, int64_t B, int K, int M, const float* coef, const float* g,
+                                   float* dUb, float* dIb, float* dUreg, float* dIreg, void* stream) {
+  TAGREC_REQUIRE(Ub && Ib && coef, "wbce_bwd: null pointer");
+  TAGREC_REQUIRE((dUb == nullptr) == (dIb == nullptr), "wbce_bwd: dUb/dIb must both be given or both null (reg-only pass)");
+  TAGREC_TRY(wbce_shape("wbce_bwd", B, D, ld, K, M));
+  TAGREC_REQUIRE(!Ureg || (Ireg && dUreg && dIreg && Dreg >= 1 && ldreg >= Dreg), "wbce_bwd: bad reg arguments");
+  TAGREC_REQUIRE(Ureg || (!Ireg && !dUreg && !dIreg), "wbce_bwd: Ireg / dUreg / dIreg given without Ureg (no L2 part to write)");
+  // one buffer for both parts: then the L2 rows must be the score rows themselves
+  TAGREC_REQUIRE(!Ureg || !dUb || ((dUreg == dUb) == (dIreg == dIb)), "wbce_bwd: dUreg/dIreg must both alias dUb/dIb or neither");
+  TAGREC_REQUIRE(!Ureg || !dUb || dUreg != dUb || (Ureg == Ub && Ireg == Ib && ldreg == ld && Dreg == D),
+                 "wbce_bwd: a gradient buffer shared by both parts needs Ureg = Ub and Ireg = Ib");
+  const int64_t blocks = (B + 3) / 4;
+  wbce_bwd_kernel<<<static_cast<unsigned>(blocks), kThreads, 0, static_cast<hipStream_t>(stream)>>>(
+      Ub, Ib, ld, D, Ureg, Ireg, ldreg, Dreg, B, K, 1 + K + M, coef, g, 1.0f / static_cast<float>(B), dUb, dIb, dUreg, dIreg);
   TAGREC_LAUNCH_CHECK();
   return TAGREC_OK;
 }

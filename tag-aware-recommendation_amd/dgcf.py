@@ -70,6 +70,7 @@ class DGCF(TableModel):
     def _config(self, config):
         _lib.refuse_deterministic(config, "DGCF", "the backward of its torch gathers sums repeated batch rows with float atomics")
         _lib.refuse_multi_negative(config, "DGCF")
+        _lib.refuse_ultragcn(config, "DGCF")
         self.dim_latent = config["dim_latent"]
         self.num_layer = len(config["dim_layer_list"])
         self.device = torch.device(config["device"])

@@ -83,6 +83,7 @@ class DisenGCN(TableModel):
     def _config(self, config):
         _lib.refuse_deterministic(config, "DisenGCN", "the backward of its torch gathers sums repeated batch rows with float atomics")
         _lib.refuse_multi_negative(config, "DisenGCN")
+        _lib.refuse_ultragcn(config, "DisenGCN")
         self.dim_latent = config["dim_latent"]
         self.num_layer = len(config["dim_layer_list"])
         self.device = torch.device(config["device"])

@@ -238,6 +238,7 @@ class DisenHAN(TableModel):
     def _config(self, config):
         _lib.refuse_deterministic(config, "DisenHAN", "the backward of its torch gathers sums repeated batch rows with float atomics")
         _lib.refuse_multi_negative(config, "DisenHAN")
+        _lib.refuse_ultragcn(config, "DisenHAN")
         self.dim_latent = config["dim_latent"]
         self.num_layer = len(config["dim_layer_list"])
         self.device = torch.device(config["device"])

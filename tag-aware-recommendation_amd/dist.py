@@ -527,6 +527,7 @@ class ShardedLightGCN(torch.nn.Module):
         super().__init__()
         _lib.refuse_deterministic(config, "ShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         _lib.refuse_multi_negative(config, "ShardedLightGCN")
+        _lib.refuse_ultragcn(config, "ShardedLightGCN")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -922,6 +923,7 @@ class ShardedNGCF(torch.nn.Module):
         super().__init__()
         _lib.refuse_deterministic(config, "ShardedNGCF", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         _lib.refuse_multi_negative(config, "ShardedNGCF")
+        _lib.refuse_ultragcn(config, "ShardedNGCF")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)
@@ -1206,6 +1208,7 @@ class FeatureShardedLightGCN(torch.nn.Module):
         super().__init__()
         _lib.refuse_deterministic(config, "FeatureShardedLightGCN", "the sharded steps fold batch gradients with index_add_ and the atomic BPR backward")
         _lib.refuse_multi_negative(config, "FeatureShardedLightGCN")
+        _lib.refuse_ultragcn(config, "FeatureShardedLightGCN")
         self.ops = ops if ops is not None else HipOps()
         self.group = group
         self.world = dist.get_world_size(group)

@@ -192,6 +192,57 @@ def ranking_loss(U, I, Ureg, Ireg, tuples, loss_func, temperature=1.0, plans=Non
     return out[0], out[1]
 
 
+class UltraTables(NamedTuple):
+    """The constants of UltraGCN's loss (Mao et al., CIKM 2021), built once from the train edges (`ultragcn_tables`)."""
+    beta_u: torch.Tensor                   # [n_user] float32: sqrt(d_u + 1) / d_u, 0 at d_u = 0
+    beta_i: torch.Tensor                   # [n_item] float32: 1 / sqrt(d_i + 1)
+    nbr_id: Optional[torch.Tensor]         # [n_item, M] int64 co-occurrence neighbours, -1 = pad; None: no neighbour term
+    nbr_w: Optional[torch.Tensor]          # [n_item, M] float32 omega, 0 at the pads
+    w: tuple = (1e-6, 1.0, 1e-6, 1.0)      # w1 .. w4
+    negative_weight: float = 10.0
+    lam: float = 1.0                       # lambda of the neighbour term
+
+
+def ultragcn_tables(edge_index, n_user, n_item, device, neighbors=10, zero_diagonal=False, w=(1e-6, 1.0, 1e-6, 1.0),
+                    negative_weight=10.0, lam=1.0, **cooc_args):
+    """`UltraTables` of the train edges [E, 2] = (user, item): the degree weights (fp64 on the host side of the edge list,
+    rounded once) and, with neighbors > 0, every item's `neighbors` heaviest co-occurrence neighbours
+    (`cooc.item_cooccurrence_topk`; cooc_args: its lds_limit / workspace_bytes)."""
+    from .cooc import cooc_csrs, item_cooccurrence_topk
+    csrs = cooc_csrs(edge_index, n_user, n_item, device)
+    du = (csrs.ui_ptr[1:] - csrs.ui_ptr[:-1]).to(torch.float64)
+    di = (csrs.iu_ptr[1:] - csrs.iu_ptr[:-1]).to(torch.float64)
+    beta_u = torch.where(du > 0, torch.sqrt(du + 1) / du.clamp(min=1), torch.zeros_like(du)).to(torch.float32)
+    beta_i = (1.0 / torch.sqrt(di + 1)).to(torch.float32)
+    nbr_id = nbr_w = None
+    if neighbors:
+        nbr_id, nbr_w, _ = item_cooccurrence_topk(None, n_user, n_item, int(neighbors), zero_diagonal, csrs=csrs, **cooc_args)
+        nbr_id = nbr_id.to(torch.int64)
+    return UltraTables(beta_u, beta_i, nbr_id, nbr_w, tuple(float(x) for x in w), float(negative_weight), float(lam))
+
+
+def ultragcn_plans(tuples, tables, n_user, n_item, width=256, stage=None):
+    """(plan of the user slots, plan of the item slots) of a [B, 2 + K] tuple batch for `ultragcn_loss(plans=...)`: the item
+    slots are the positive, the K negatives and the positive's neighbours, in the stage's slot order.  stage (an
+    `loss_stage.Ultra` of `tables`, made for THIS batch): its slot ids are built here and reused by `ultragcn_loss(stage=...)`,
+    so the neighbour gather runs once per step."""
+    uid, iid = (stage if stage is not None else S.Ultra(tables)).ids(tuples)
+    return rowops.row_list_plan(uid, n_user, None, width), rowops.row_list_plan(iid, n_item, None, width)
+
+
+def ultragcn_loss(U, I, Ureg, Ireg, tuples, tables, plans=None, stage=None):
+    """(mul_loss, l2reg_loss) of a [B, 2 + K] batch (user, positive, K >= 1 negatives) under UltraGCN's objective as a MEAN
+    over the batch (the paper's code sums): with s = u . i, b_u = sqrt(d_u + 1) / d_u and b_i = 1 / sqrt(d_i + 1),
+        mul_loss = (1 / B) sum_b [ (w1 + w2 b_u b_p) softplus(-s_p) + (negative_weight / K) sum_k (w3 + w4 b_u b_nk) softplus(s_nk)
+                                   + lam sum_{j in top-M co-occurrence neighbours of p} omega_pj softplus(-s_j) ]
+    l2reg_loss = 0.5 (|u|^2 + |p|^2 + sum_k |n_k|^2) / B on the rows of Ureg / Ireg (None: 0; the neighbour rows carry none).
+    tables: `ultragcn_tables`.  plans (`ultragcn_plans`): the compact gradients are folded onto the tables in a fixed order (the
+    same bits every run) instead of by `index_add_`.  stage: the `loss_stage.Ultra` that `ultragcn_plans` was handed for this
+    batch (None: a new one)."""
+    out = stage_loss(stage if stage is not None else S.Ultra(tables), U, I, Ureg, Ireg, tuples, plans)
+    return out[0], out[1]
+
+
 class InBatchRoute(NamedTuple):
     """What a fused step is handed in place of `rank_route`'s (K, temperature) when the model has negatives="in_batch"."""
     temperature: float

@@ -45,6 +45,7 @@ class KGAT(nn.Module):
     def _config(self, config):
         _lib.refuse_deterministic(config, "KGAT", "the backward of its torch gathers sums repeated batch rows with float atomics")
         _lib.refuse_multi_negative(config, "KGAT")
+        _lib.refuse_ultragcn(config, "KGAT")
         self.dim_latent = config["dim_latent"]
         self.dim_relation = config["dim_relation"]
         self.dim_layer_list = list(config["dim_layer_list"])

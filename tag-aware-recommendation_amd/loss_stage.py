@@ -103,6 +103,60 @@ class Rank(_Stage):
         rowops.rank_bwd(Ub, Ib, Ureg, Ireg, self.coef, g, dUb, dIb, dUreg, dIreg, *self._what("rank_bwd", what))
 
 
+class Ultra(_Stage):
+    """[B, 2 + K] = (user, positive, K negatives) under UltraGCN's weighted pointwise BCE (`rowops.wbce_fwd` / `wbce_bwd`):
+    the M co-occurrence neighbours of the positive (`tables.nbr_id[positive]`) follow the negatives as slots K + 1 .. K + M.
+    A pad (-1) is replaced by the positive's own id and weighs 0, so its gradient is an exact zero.  tables:
+    `help.UltraTables`.  The [B, 1 + K + M] weights are gathered on the stream; nothing reads the host."""
+    name, batch_word = "ultragcn_loss", "tuples"
+
+    def __init__(self, tables):
+        self.tables = tables
+        self.M = 0 if tables.nbr_id is None else tables.nbr_id.shape[1]
+
+    def check(self, name, batch):
+        if batch.dim() != 2 or batch.shape[1] < 3 or batch.shape[0] < 1:
+            raise _lib.TagrecError(f"{name}: tuples {tuple(batch.shape)} must be [B, 2 + K] = (user, positive, K >= 1 negatives)")
+        if 1 + (batch.shape[1] - 2) + self.M > rowops.WBCE_MAX_SLOTS:
+            raise _lib.TagrecError(f"{name}: {batch.shape[1] - 2} negatives and {self.M} neighbours exceed the "
+                                   f"{rowops.WBCE_MAX_SLOTS} slots of a tuple")
+
+    def rows(self, batch, n_user):
+        uid, iid = self.ids(batch)
+        return torch.cat([uid, n_user + iid])
+
+    def ids(self, batch):
+        if self._ids is None:
+            t = self.tables
+            uid, pos = batch[:, 0].contiguous(), batch[:, 1]
+            items = batch[:, 1:]
+            if self.M:
+                nb = t.nbr_id.index_select(0, pos)                                   # [B, M] int64, -1 = pad
+                items = torch.cat([items, torch.where(nb < 0, pos.unsqueeze(1), nb)], dim=1)
+            self._ids = (uid, items.t().contiguous().view(-1))
+        return self._ids
+
+    def weights(self, batch):
+        """[B, 1 + K + M]: positive w1 + w2 b_u b_i; negative (w3 + w4 b_u b_j) negative_weight / K; neighbour lambda omega."""
+        t = self.tables
+        uid, pos, neg = batch[:, 0], batch[:, 1], batch[:, 2:]
+        w1, w2, w3, w4 = t.w
+        bu = t.beta_u.index_select(0, uid).unsqueeze(1)
+        parts = [w1 + w2 * bu * t.beta_i.index_select(0, pos).unsqueeze(1),
+                 (w3 + w4 * bu * t.beta_i[neg]) * (t.negative_weight / neg.shape[1])]
+        if self.M:
+            parts.append(t.lam * t.nbr_w.index_select(0, pos))
+        return torch.cat(parts, dim=1).contiguous()
+
+    def fwd(self, batch, Ub, Ib, Ureg, Ireg):
+        self.K = batch.shape[1] - 2
+        res, self.coef = rowops.wbce_fwd(Ub, Ib, Ureg, Ireg, self.weights(batch), self.K, self.M)
+        return res
+
+    def bwd(self, Ub, Ib, Ureg, Ireg, g, dUb, dIb, dUreg, dIreg, what=None):
+        rowops.wbce_bwd(Ub, Ib, Ureg, Ireg, self.coef, g, dUb, dIb, dUreg, dIreg, self.K, self.M, *self._what("wbce_bwd", what))
+
+
 class InBatch(_Stage):
     """[B, 2] = (user, positive), the other positives are the negatives: the fused B x B kernels `rowops.inbatch_fwd` /
     `inbatch_bwd` with the batch's ids as masks and item_logq ([n_item], or None) as the column bias."""

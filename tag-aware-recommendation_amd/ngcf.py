@@ -418,6 +418,7 @@ class NGCF(FusedStepModel):
         self.split_adj_k = config["split_adj_k"]
         self.reg = config["reg"]
         # K negatives per positive: batches are [B, 2 + K]; K > 1 or "softmax" takes the multi-negative loss kernels
+        _lib.refuse_ultragcn(config, type(self).__name__)       # the ug_* keys are UltraGCN's: refused, not ignored
         self.n_negatives, self.loss_func, self.loss_temperature = check_ranking(config)
         # negatives="in_batch": [B, 2] batches, the other positives of the batch are the negatives (rowops.inbatch_*)
         self.in_batch, self.in_batch_logq = check_negatives(config)

@@ -240,6 +240,68 @@ def rank_bwd(Ub, Ib, Ureg, Ireg, coef, g, dUb, dIb, dUreg, dIreg, what="rank_bwd
           what)
 
 
+# ---- weighted pointwise binary cross-entropy on compact rows (UltraGCN) ----
+
+WBCE_MAX_SLOTS = 4096    # S = 1 + K + M: the kernels loop over the slots, the bound keeps a tuple's work in one wave sane
+
+
+def _wbce_shape(what, Ub, Ib, K, M):
+    """(B, S) of a compact operand pair Ub [B, D] / Ib [S B, D], S = 1 + K + M."""
+    if Ub is None or Ib is None or Ub.dim() != 2 or Ib.dim() != 2:
+        raise _lib.TagrecError(f"{what}: Ub and Ib must be 2-d tensors")
+    if isinstance(K, bool) or isinstance(M, bool) or not isinstance(K, int) or not isinstance(M, int) or K < 1 or M < 0 \
+            or 1 + K + M > WBCE_MAX_SLOTS:
+        raise _lib.TagrecError(f"{what}: K={K!r} / M={M!r} must be integers with K >= 1, M >= 0 and 1 + K + M <= {WBCE_MAX_SLOTS}")
+    B, S = Ub.shape[0], 1 + K + M
+    if B < 1 or Ib.shape[0] != S * B:
+        raise _lib.TagrecError(f"{what}: Ub {tuple(Ub.shape)} / Ib {tuple(Ib.shape)} must be [B, D] / [(1 + K + M) B, D] "
+                               f"with K={K}, M={M}")
+    return B, S
+
+
+def _wbce_reg_rows(what, Ureg, Ireg, B, S):
+    if Ureg is not None and Ireg is not None and (Ureg.shape[0] != B or Ireg.shape[0] != S * B):
+        raise _lib.TagrecError(f"{what}: Ureg {tuple(Ureg.shape)} / Ireg {tuple(Ireg.shape)} must have {B} / {S * B} rows")
+
+
+def wbce_fwd(Ub, Ib, Ureg, Ireg, weight, K, M=0):
+    """Weighted pointwise BCE of B tuples on gathered rows: Ub [B, D] users, Ib [S B, D] items, S = 1 + K + M (slot j of tuple
+    b at row j B + b; j = 0 the positive, 1 .. K the negatives, K + 1 .. K + M the positive's neighbours); labels +1 / -1 /
+    +1; weight [B, S] float32 >= 0.  mul_loss = (1 / B) sum w softplus(-t s); the L2 part reads Ureg and slots 0 .. K of Ireg
+    (None: no L2 term).  -> (res = [mul_loss, l2reg_loss (unweighted)], coef [B, S] for `wbce_bwd`, 1 / B folded in)."""
+    B, S = _wbce_shape("wbce_fwd", Ub, Ib, K, M)
+    ld, D = _pair_ld("wbce_fwd", ("Ub", "Ib"), Ub, Ib)
+    ldreg, dreg = _pair_ld("wbce_fwd", ("Ureg", "Ireg"), Ureg, Ireg)
+    _wbce_reg_rows("wbce_fwd", Ureg, Ireg, B, S)
+    if not isinstance(weight, torch.Tensor) or weight.shape != (B, S) or not weight.is_contiguous():
+        raise _lib.TagrecError(f"wbce_fwd: weight must be a contiguous [{B}, {S}] tensor")
+    coef = torch.empty(B, S, dtype=torch.float32, device=Ub.device)
+    partials = torch.empty(2 * ((B + 3) // 4), dtype=torch.float32, device=Ub.device)     # two floats per launched block
+    res = torch.empty(2, dtype=torch.float32, device=Ub.device)
+    check(load().tagrec_wbce_fwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, K, M, weight, coef, partials, res, stream_ptr()),
+          "wbce_fwd")
+    return res, coef
+
+
+def wbce_bwd(Ub, Ib, Ureg, Ireg, coef, g, dUb, dIb, dUreg, dIreg, K, M=0, what="wbce_bwd"):
+    """STORES the gradients of `wbce_fwd`'s two loss parts into every row of dUb / dIb and dUreg / dIreg (zeros in the L2 rows
+    of the neighbour slots) -- no atomics, the old contents are not read.  The None forms and the one-buffer form are
+    `rank_bwd`'s: dUb = dIb = None: the L2 part only; Ureg = Ireg = None: no L2 part; dUreg is dUb and dIreg is dIb (with Ureg
+    is Ub, Ireg is Ib): one buffer takes the sum."""
+    B, S = _wbce_shape(what, Ub, Ib, K, M)
+    g = None if g is None else g.contiguous()
+    ld, D = _pair_ld(what, ("Ub", "Ib"), Ub, Ib, (dUb, dIb))
+    ldreg, dreg = _pair_ld(what, ("Ureg", "Ireg"), Ureg, Ireg, (dUreg, dIreg))
+    _wbce_reg_rows(what, Ureg, Ireg, B, S)
+    if coef.shape != (B, S) or not coef.is_contiguous():
+        raise _lib.TagrecError(f"{what}: coef {tuple(coef.shape)} must be a contiguous [{B}, {S}] tensor")
+    for nm, t, n in (("dUb", dUb, B), ("dIb", dIb, S * B), ("dUreg", dUreg, B), ("dIreg", dIreg, S * B)):
+        if t is not None and t.shape[0] != n:
+            raise _lib.TagrecError(f"{what}: {nm} {tuple(t.shape)} must have {n} rows")
+    check(load().tagrec_wbce_bwd_f32(Ub, Ib, ld, D, Ureg, Ireg, ldreg, dreg, B, K, M, coef, g, dUb, dIb, dUreg, dIreg, stream_ptr()),
+          what)
+
+
 # ---- in-batch sampled softmax on compact rows: the fused B x B loss (csrc/inbatch.hip) ----
 
 INBATCH_TILE = 64        # rows per block of the in-batch kernels: `partials` holds two floats per block

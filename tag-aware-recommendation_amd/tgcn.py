@@ -627,6 +627,7 @@ class TGCN(nn.Module):
     def _config(self, config):
         _lib.refuse_deterministic(config, "TGCN", "the attention backward's scatter forms, the segmented dQ and the TransTag backward sum with float atomics")
         _lib.refuse_multi_negative(config, "TGCN")
+        _lib.refuse_ultragcn(config, "TGCN")
         self.dim_latent = config["dim_latent"]
         self.dim_weight = config["dim_weight"]
         self.num_layer = len(config["dim_layer_list"])

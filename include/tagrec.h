@@ -736,6 +736,37 @@ int tagrec_adam_multi_f32(int n_tensors, float* const* p, const float* const* g,
 int tagrec_adam_graph_f32(float* p, const float* g, float* m, float* v, int64_t n,
                           float lr, float b1, float b2, float eps, int64_t* step_dev, float* coef_dev, void* stream);
 
+/* Row-sparse Adam that computes what tagrec_adam_f32 computes, bit for bit (train.RowAdam).  Under a zero gradient the update
+ * of a row is a function of the row's own p / m / v and of two per-step scalars, so a row the step does not name is left
+ * alone and the skipped steps are replayed, in order, when it is next read.  State per table p / m / v [n_rows, D] (row
+ * stride ld): last (int32 [n_rows]) = the last optimizer step applied to each row, and a ring of cap float pairs in device
+ * memory, (lr / (1 - b1^t), sqrt(1 - b2^t)) of step t at entry t mod cap.
+ *   adam_coef : HOST ONLY, no stream.  Fills the host array out [2 n] with the pairs of steps t0 .. t0 + n - 1 (t0 >= 1) --
+ *               the double-precision expressions of tagrec_adam_f32, each rounded to float once.  (tagrec_adam_f32 takes lr /
+ *               b1 / b2 as floats and widens them: pass the widened values here to get its bits.)
+ *   catchup   : every distinct row r of a built row-list plan (ws, n_listed, width as for tagrec_row_scatter_ordered_f32)
+ *               takes the zero-gradient update of steps last[r] + 1 .. t_done, in order; p, m, v and last[r] = t_done are
+ *               stored.  A row with last[r] == t_done is not read beyond `last`.
+ *   apply     : the gradient of every distinct row is its segment's sum of src [n_listed, D] (row stride lds) in EXACTLY
+ *               tagrec_row_scatter_ordered_f32's order (the same device code); one update of step t with the ring's pair of t;
+ *               last[r] = t.  Requires last[r] == t - 1 on entry (run catchup to t - 1 first); not checked on the device.
+ *   flush     : every row of the table with last[r] < t_done is replayed to t_done.  A row that is current costs its 4 bytes
+ *               of `last`; a 16-byte column group whose m and v are all +0 bits is left as it is (exact: a zero gradient
+ *               does not change it) and its p is not read.
+ * t_floor (catchup, flush): a lower bound of last[] over the rows concerned, kept by the caller (the step of its last flush);
+ * the ring entries of steps t_floor + 1 .. t_done must be filled, t_done - t_floor <= min(cap, 4096) (a block stages that
+ * window in LDS).  A row whose `last` is below t_floor is replayed from t_floor.  D in {8, .., 256} with 16-byte aligned rows
+ * takes D / 4 lanes x 16 bytes per row, anything else one lane per column.  No float atomics, no host read. */
+int tagrec_adam_coef(double lr, double b1, double b2, int64_t t0, int64_t n, float* out);
+int tagrec_rowadam_catchup_f32(const void* ws, int64_t ws_bytes, int64_t n_listed, int width, float* p, float* m, float* v,
+                               int64_t ld, int64_t n_rows, int D, int32_t* last, const float* ring, int64_t ring_cap,
+                               int64_t t_floor, int64_t t_done, float b1, float b2, float eps, void* stream);
+int tagrec_rowadam_apply_f32(const void* ws, int64_t ws_bytes, int64_t n_listed, int width, const float* src, int64_t lds,
+                             float* p, float* m, float* v, int64_t ld, int64_t n_rows, int D, int32_t* last, const float* ring,
+                             int64_t ring_cap, int64_t t, float b1, float b2, float eps, void* stream);
+int tagrec_rowadam_flush_f32(float* p, float* m, float* v, int64_t ld, int64_t n_rows, int D, int32_t* last, const float* ring,
+                             int64_t ring_cap, int64_t t_floor, int64_t t_done, float b1, float b2, float eps, void* stream);
+
 /* The last backward hop with the optimizer folded in (training/basic_train.py:19-25: backward() then opt.step()):
  * row r of A G_in + b_scale B is the gradient of parameter row r; torch.optim.Adam's update (defaults; the arithmetic of
  * tagrec_adam_f32 at step `step`, counted from 1) is applied to p / m / v [n_rows, D] in the epilogue and no gradient

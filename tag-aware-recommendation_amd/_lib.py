@@ -124,6 +124,7 @@ class U64Ptr(Ptr):
 
 # C type of include/tagrec.h (const dropped, the stars joined to the base type) -> argtype
 _CTYPES = {"int": c_int, "int32_t": ctypes.c_int32, "int64_t": c_int64, "uint64_t": ctypes.c_uint64, "float": c_float,
+           "double": ctypes.c_double,
            "float*": F32Ptr, "double*": F64Ptr, "int64_t*": I64Ptr, "int32_t*": I32Ptr, "int*": I32Ptr, "uint8_t*": U8Ptr,
            "unsigned*": U32Ptr, "uint64_t*": U64Ptr, "void*": Ptr, "char*": Ptr, "tagrec_graph*": Ptr,
            "float**": Ptr, "int32_t**": Ptr, "int64_t**": Ptr, "tagrec_graph**": Ptr}

@@ -138,6 +138,15 @@ __device__ __forceinline__ adam_f4 adam_update(adam_f4& mi, adam_f4& vi, adam_f4
   }
   return pi;
 }
+// The two step-dependent factors of that update, lr / (1 - b1^t) and sqrt(1 - b2^t): torch's host arithmetic (python
+// floats = doubles), each rounded to float once.  The one statement of it: tagrec_adam_f32 and the coefficient ring of
+// the row-sparse Adam (tagrec_adam_coef) must agree to the bit.
+inline void adam_step_coef(double lr, double b1, double b2, int64_t step, float* step_size, float* bc2_sqrt) {
+  const double bc1 = 1.0 - pow(b1, static_cast<double>(step));
+  const double bc2 = 1.0 - pow(b2, static_cast<double>(step));
+  *step_size = static_cast<float>(lr / bc1);
+  *bc2_sqrt = static_cast<float>(sqrt(bc2));
+}
 // Optional Adam update in place of a gradient store (EpiArgs::adam): p == nullptr -> off
 struct AdamRow {
   float* p; float* m; float* v;

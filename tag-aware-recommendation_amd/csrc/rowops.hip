@@ -1129,10 +1129,9 @@ extern "C" int tagrec_adam_f32(float* p, const float* g, float* m, float* v, int
   TAGREC_REQUIRE(n >= 0 && step >= 1, "adam: bad n or step");
   if (n == 0) return TAGREC_OK;
   // same host arithmetic as torch's _single_tensor_adam (python floats = doubles)
-  const double bc1 = 1.0 - pow(static_cast<double>(b1), static_cast<double>(step));
-  const double bc2 = 1.0 - pow(static_cast<double>(b2), static_cast<double>(step));
-  return launch_adam(p, g, m, v, n, b1, b2, eps, static_cast<float>(static_cast<double>(lr) / bc1),
-                     static_cast<float>(sqrt(bc2)), nullptr, static_cast<hipStream_t>(stream));
+  float step_size, bc2_sqrt;
+  adam_step_coef(static_cast<double>(lr), static_cast<double>(b1), static_cast<double>(b2), step, &step_size, &bc2_sqrt);
+  return launch_adam(p, g, m, v, n, b1, b2, eps, step_size, bc2_sqrt, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // Many small parameter tensors in ONE launch (a TGCN layer has 21; one launch each costs more in launch latency than in

@@ -20,40 +20,19 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "common.h"
+#include "rowlist.h"
 
 namespace tagrec {
 namespace {
 
-constexpr int kScatterChunk = 1024;      // slots per chain (= kLongRow of the CSR kernels)
-constexpr int kScatterWaves = 4;         // wavefronts per block
 constexpr int kThreads = 256;
-
-// ---- workspace layout (bytes, every part 256-byte aligned) ----
-struct RowListLayout {
-  size_t order, seg_row, seg_ptr, counts, seg_of, slab, keys_in, keys_out, slots_in, head, tmp, tmp_sort, tmp_scan, total;
-};
-enum { kCountSegments = 0, kCountValid = 1, kCountBad = 2 };   // counts[4] (int32)
-
-size_t up256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
-
-int64_t slab_rows(int64_t n_listed) { return n_listed > kScatterChunk ? 2 * ((n_listed + kScatterChunk - 1) / kScatterChunk) : 0; }
 
 // with_tmp = false: the parts a scatter reads (everything up to the slab); `total` then ends there and no rocPRIM size query is made
 int rowlist_layout(int64_t n_listed, int width, RowListLayout* L, bool with_tmp = true) {
-  size_t o = 0;
+  size_t o = rowlist_layout_head(n_listed, width, L);
+  if (!with_tmp) return TAGREC_OK;
   auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
   const size_t T = static_cast<size_t>(n_listed);
-  L->order = take(T * sizeof(int32_t));
-  L->seg_row = take(T * sizeof(int32_t));
-  L->seg_ptr = take((T + 1) * sizeof(int32_t));
-  L->counts = take(4 * sizeof(int32_t));
-  L->seg_of = take(T * sizeof(int32_t));
-  L->slab = take(static_cast<size_t>(slab_rows(n_listed)) * width * sizeof(float));
-  if (!with_tmp) {
-    L->total = o;
-    return TAGREC_OK;
-  }
   L->keys_in = take(T * sizeof(uint32_t));
   L->keys_out = take(T * sizeof(uint32_t));
   L->slots_in = take(T * sizeof(int32_t));
@@ -67,12 +46,6 @@ int rowlist_layout(int64_t n_listed, int width, RowListLayout* L, bool with_tmp 
   L->tmp_scan = scan_bytes;
   L->tmp = take(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
   L->total = o;
-  return TAGREC_OK;
-}
-
-int check_list(const char* who, int64_t n_listed, int width) {
-  TAGREC_REQUIRE(n_listed >= 1 && n_listed < (1ll << 30), std::string(who) + ": the list holds 1 .. 2^30 - 1 rows");
-  TAGREC_REQUIRE(width >= 1 && width <= (1 << 16), std::string(who) + ": the width must be 1 .. 65536");
   return TAGREC_OK;
 }
 
@@ -118,59 +91,16 @@ __global__ __launch_bounds__(kThreads) void rowlist_segments_kernel(const uint32
   }
 }
 
-// ---- scatter ----
-struct ScatterPlan {        // device view of a built plan
-  const int32_t* order;     // [n_listed] slot ids by (row, slot)
-  const int32_t* seg_row;   // [S]
-  const int32_t* seg_ptr;   // [S + 1]
-  const int32_t* seg_of;    // [n_listed] inclusive head scan
-  const int32_t* counts;
-  int32_t n_listed;
-};
-
-__device__ __forceinline__ float vadd(float a, float b) { return a + b; }
-__device__ __forceinline__ float4 vadd(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-__device__ __forceinline__ int64_t slab_slot(int32_t pos, bool first_chunk) { return 2 * static_cast<int64_t>(pos >> 10) + (first_chunk ? 1 : 0); }
-
-// One column (V = float) or one 16-byte column group (V = float4) of the work of sorted position i.  src / dst / slab point
-// at that column; lds / ldd / lslab are row strides in units of V.
-//   FOLD = false: position i opens a chunk -> chain over the chunk; the sum lands on dst (short segment) or in the slab.
-//   FOLD = true : position i opens a LONG segment -> its chunk sums, left to right, land on dst.
-template <typename V, bool FOLD>
-__device__ __forceinline__ void scatter_column(const ScatterPlan& pl, int32_t i, const V* __restrict__ src, int64_t lds, V* __restrict__ dst,
-                                               int64_t ldd, V* __restrict__ slab, int64_t lslab, int64_t n_dst, int accumulate) {
-  const int32_t s = pl.seg_of[i] - 1;
-  const int32_t start = pl.seg_ptr[s];
-  const int32_t len = pl.seg_ptr[s + 1] - start;
-  const int32_t rel = i - start;
-  V acc;
-  if constexpr (!FOLD) {
-    if (rel & (kScatterChunk - 1)) return;
-    const int32_t m = min(kScatterChunk, len - rel);
-    const int32_t* __restrict__ ord = pl.order + i;
-    acc = src[static_cast<int64_t>(ord[0]) * lds];
-    int32_t t = 1;
-    for (; t + 4 <= m; t += 4) {                       // four rows in flight, added in slot order
-      const V x0 = src[static_cast<int64_t>(ord[t]) * lds], x1 = src[static_cast<int64_t>(ord[t + 1]) * lds];
-      const V x2 = src[static_cast<int64_t>(ord[t + 2]) * lds], x3 = src[static_cast<int64_t>(ord[t + 3]) * lds];
-      acc = vadd(acc, x0); acc = vadd(acc, x1); acc = vadd(acc, x2); acc = vadd(acc, x3);
-    }
-    for (; t < m; ++t) acc = vadd(acc, src[static_cast<int64_t>(ord[t]) * lds]);
-    if (len > kScatterChunk) {
-      slab[slab_slot(i, rel == 0) * lslab] = acc;
-      return;
-    }
-  } else {
-    if (rel != 0 || len <= kScatterChunk) return;
-    acc = slab[slab_slot(start, true) * lslab];
-    for (int32_t p = start + kScatterChunk; p < start + len; p += kScatterChunk) acc = vadd(acc, slab[slab_slot(p, false) * lslab]);
+// ---- scatter (the segment sum itself: scatter_column of rowlist.h) ----
+// where a finished segment sum lands: one store, or one fp32 add, per segment and column
+template <typename V>
+struct LandOnRow {
+  V* dst; int64_t ldd; int accumulate;
+  __device__ __forceinline__ void operator()(int64_t row, const V& acc) const {
+    V* d = dst + row * ldd;
+    *d = accumulate ? vadd(*d, acc) : acc;
   }
-  const int64_t row = pl.seg_row[s];
-  if (row < 0 || row >= n_dst) return;                 // (the plan admits ids of [0, n) only; n_dst >= n is checked on the host)
-  V* d = dst + row * ldd;
-  *d = accumulate ? vadd(*d, acc) : acc;
-}
+};
 
 // Lane group q of a wave owns sorted position (wave * NPI + q), lane c of the group its float4 column c.
 template <int LPR, bool FOLD>
@@ -184,7 +114,8 @@ __global__ __launch_bounds__(kScatterWaves * kWave) void row_scatter_vec_kernel(
   const int64_t i = wv * NPI + q;
   if (i >= pl.n_listed || i >= pl.counts[kCountValid]) return;
   scatter_column<float4, FOLD>(pl, static_cast<int32_t>(i), reinterpret_cast<const float4*>(src) + c, lds / 4,
-                               reinterpret_cast<float4*>(dst) + c, ldd / 4, reinterpret_cast<float4*>(slab) + c, LPR, n_dst, accumulate);
+                               reinterpret_cast<float4*>(slab) + c, LPR, n_dst,
+                               LandOnRow<float4>{reinterpret_cast<float4*>(dst) + c, ldd / 4, accumulate});
 }
 
 // Any width: one wavefront per sorted position, lane c takes columns c, c + 64, ...
@@ -197,7 +128,7 @@ __global__ __launch_bounds__(kScatterWaves * kWave) void row_scatter_scalar_kern
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kScatterWaves + (threadIdx.x >> 6);
   if (i >= pl.n_listed || i >= pl.counts[kCountValid]) return;
   for (int c = lane; c < D; c += kWave)
-    scatter_column<float, FOLD>(pl, static_cast<int32_t>(i), src + c, lds, dst + c, ldd, slab + c, D, n_dst, accumulate);
+    scatter_column<float, FOLD>(pl, static_cast<int32_t>(i), src + c, lds, slab + c, D, n_dst, LandOnRow<float>{dst + c, ldd, accumulate});
 }
 
 template <int LPR>
@@ -307,9 +238,7 @@ extern "C" int tagrec_row_scatter_ordered_f32(const void* ws, int64_t ws_bytes, 
   if (rc != TAGREC_OK) return rc;
   TAGREC_REQUIRE(ws_bytes >= static_cast<int64_t>(L.total), "row_scatter_ordered: workspace smaller than tagrec_rowlist_workspace(...)");
   const char* base = static_cast<const char*>(ws);
-  const ScatterPlan pl{reinterpret_cast<const int32_t*>(base + L.order), reinterpret_cast<const int32_t*>(base + L.seg_row),
-                       reinterpret_cast<const int32_t*>(base + L.seg_ptr), reinterpret_cast<const int32_t*>(base + L.seg_of),
-                       reinterpret_cast<const int32_t*>(base + L.counts), static_cast<int32_t>(n_listed)};
+  const ScatterPlan pl = scatter_plan(ws, L, n_listed);
   float* slab = reinterpret_cast<float*>(const_cast<char*>(base) + L.slab);     // scratch of the launch in flight: one stream per plan
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool vec = aligned16(src) && aligned16(dst) && lds % 4 == 0 && ldd % 4 == 0;

@@ -152,6 +152,50 @@ class _GatheredRowsLoss(torch.autograd.Function):
         return dU, dI, None, None, None, None, None
 
 
+class _RowSparseLoss(torch.autograd.Function):
+    """`_GatheredRowsLoss` on ONE [user | item] table under a row optimizer (`train.RowAdam`), the L2 part on the same rows:
+    one plan over the stage's rows, which are caught up to the optimizer's step before they are gathered; the backward
+    hands (plan, compact gradient) to the optimizer and returns NO gradient for the table -- `table.grad` stays None and
+    nothing table-sized is allocated.  Returns [mul_loss, l2reg_loss (unweighted)]."""
+
+    @staticmethod
+    def forward(ctx, table, batch, stage, n_user, opt, owner):
+        # owner[0]: the parameter itself, the optimizer's key for the table (`table` may be autograd's alias of it)
+        name = stage.name
+        if not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
+            raise _lib.TagrecError(f"{name}: the table must be a 2-d float32 GPU tensor")
+        batch = _lib.require_gpu_tensor(batch.contiguous(), torch.int64, f"{name} {stage.batch_word}")
+        stage.check(name, batch)
+        rows = stage.rows(batch, n_user)                 # the user slots, then the item slots shifted by n_user
+        plan = rowops.row_list_plan(rows, table.shape[0], None, table.shape[1])
+        opt.catch_up(owner[0], plan)
+        B = batch.shape[0]
+        Tb = table.detach().index_select(0, rows)
+        Ub, Ib = Tb[:B], Tb[B:]
+        res = stage.fwd(batch, Ub, Ib, Ub, Ib)
+        ctx.saved = (owner[0], Tb, plan, B)
+        ctx.stage, ctx.opt = stage, opt
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        param, Tb, plan, B = ctx.saved
+        d = torch.empty_like(Tb)
+        Ub, Ib, dUb, dIb = Tb[:B], Tb[B:], d[:B], d[B:]
+        ctx.stage.bwd(Ub, Ib, Ub, Ib, g, dUb, dIb, dUb, dIb)       # reg on the same rows: one gradient buffer
+        ctx.opt.row_grad(param, plan, d)
+        return None, None, None, None, None, None
+
+
+def ultragcn_row_loss(table, n_user, tuples, tables, opt, stage=None):
+    """`ultragcn_loss` of the [user | item] `table` (both parts on the same rows) for a training step under the row
+    optimizer `opt` (`train.RowAdam`, attached): the same values, but the gradient goes to the optimizer as (plan, compact
+    rows) and the table receives none.  The fold order is `ultragcn_plans`' -- a row's slots ascending, the user slots
+    before the item slots -- whatever `deterministic` says."""
+    out = _RowSparseLoss.apply(table, tuples, stage if stage is not None else S.Ultra(tables), n_user, opt, (table,))
+    return out[0], out[1]
+
+
 def stage_loss(stage, U, I, Ureg, Ireg, batch, plans=None):
     """[mul_loss, l2reg_loss (unweighted), *stage.extra] of `batch` against user / item tables under a loss stage: what the
     fused steps' autograd nodes return, operator by operator.  The triplet stage gathers inside its kernels (`_TripletLoss`)."""

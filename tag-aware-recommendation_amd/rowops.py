@@ -717,3 +717,94 @@ def bpr_bwd_ordered(out, ego, trip, coef, g, d_out, d_ego, plan, accumulate=Fals
         scatter_rows_ordered(d_out, plan, d_b, accumulate)
     if d_e is not None and d_e is not d_b:
         scatter_rows_ordered(d_ego, plan, d_e, accumulate)
+
+
+# ---- row-sparse Adam (csrc/rowadam.hip): the kernels behind train.RowAdam ----
+
+ADAM_MAX_WINDOW = 4096   # steps one replay can span (the kernels stage that window of the ring in LDS)
+
+
+def adam_coef(lr, b1, b2, t0, n):
+    """The ring's pairs of steps t0 .. t0 + n - 1 as a CPU float32 tensor [n, 2] = (lr / (1 - b1^t), sqrt(1 - b2^t)): host
+    arithmetic only (`tagrec_adam_coef`), no stream.  lr / b1 / b2 are taken as doubles; `tagrec_adam_f32` widens floats,
+    so a caller that wants its bits passes the float-rounded values."""
+    if t0 < 1 or n < 0:
+        raise _lib.TagrecError(f"adam_coef: t0={t0} / n={n}: steps are counted from 1")
+    buf = (_lib.ctypes.c_float * (2 * n))()
+    check(load().tagrec_adam_coef(float(lr), float(b1), float(b2), int(t0), int(n), buf), "adam_coef")
+    if n == 0:
+        return torch.empty(0, 2, dtype=torch.float32)
+    return torch.frombuffer(buf, dtype=torch.float32).view(n, 2)
+
+
+def _row_adam_args(what, p, m, v, last, ring):
+    """The table side of the three row-Adam kernels -> (row stride, n_rows, D, ring capacity)."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 2 or not p.is_cuda or p.dtype != torch.float32:
+        raise _lib.TagrecError(f"{what}: p must be a 2-d float32 GPU tensor")
+    n, D = p.shape
+    ld = p.stride(0) if n > 1 else D
+    for nm, t in (("p", p), ("m", m), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.shape != p.shape or t.dtype != torch.float32 or t.device != p.device:
+            raise _lib.TagrecError(f"{what}: {nm} must be a float32 tensor {tuple(p.shape)} on {p.device}")
+        if (D > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) != ld) or ld < D:
+            raise _lib.TagrecError(f"{what}: {nm} must have unit inner stride and the row stride of p ({ld})")
+    if not isinstance(last, torch.Tensor) or last.shape != (n,) or last.dtype != torch.int32 or last.device != p.device \
+            or not last.is_contiguous():
+        raise _lib.TagrecError(f"{what}: last must be a contiguous int32 tensor [{n}] on {p.device}")
+    if not isinstance(ring, torch.Tensor) or ring.dim() != 2 or ring.shape[1] != 2 or ring.shape[0] < 1 or ring.dtype != torch.float32 \
+            or ring.device != p.device or not ring.is_contiguous():
+        raise _lib.TagrecError(f"{what}: ring must be a contiguous float32 tensor [capacity, 2] on {p.device}")
+    return ld, n, D, ring.shape[0]
+
+
+def _row_adam_window(what, cap, t_floor, t_done):
+    if not 0 <= t_floor <= t_done or t_done - t_floor > min(cap, ADAM_MAX_WINDOW):
+        raise _lib.TagrecError(f"{what}: t_floor={t_floor} / t_done={t_done}: needs 0 <= t_floor <= t_done and at most "
+                               f"min(the ring's {cap}, {ADAM_MAX_WINDOW}) steps between them")
+
+
+def _row_adam_plan(what, plan, n, D, p):
+    if not isinstance(plan, RowListPlan) or plan.n > n or plan.width < D or plan.workspace.device != p.device:
+        raise _lib.TagrecError(f"{what}: plan must be a row_list_plan over at most {n} rows, of width >= {D}, on {p.device}")
+
+
+def adam_catch_up(plan, p, m, v, last, ring, t_floor, t_done, betas=(0.9, 0.999), eps=1e-8):
+    """Every distinct row r of `plan` takes Adam's zero-gradient update of steps last[r] + 1 .. t_done, in order (what dense
+    Adam did to it while it was left alone); last[r] = t_done.  Rows the plan does not name are not touched.  p / m / v
+    [n, D] (a shared row stride), last int32 [n], ring float32 [capacity, 2] (`adam_coef`'s pair of step t at t mod
+    capacity), t_floor: a lower bound of `last` over the listed rows (rowops.ADAM_MAX_WINDOW bounds t_done - t_floor)."""
+    what = "adam_catch_up"
+    ld, n, D, cap = _row_adam_args(what, p, m, v, last, ring)
+    _row_adam_plan(what, plan, n, D, p)
+    _row_adam_window(what, cap, t_floor, t_done)
+    check(load().tagrec_rowadam_catchup_f32(plan.workspace, plan.workspace.numel(), plan.rows.numel(), plan.width, p, m, v, ld, n, D,
+                                            last, ring, cap, int(t_floor), int(t_done), float(betas[0]), float(betas[1]), float(eps),
+                                            stream_ptr()), what)
+
+
+def adam_apply_rows(plan, src, p, m, v, last, ring, t, betas=(0.9, 0.999), eps=1e-8):
+    """One Adam step, number t, of the distinct rows of `plan`: a row's gradient is the sum of src[j] over plan.rows[j] == r
+    in `scatter_rows_ordered`'s order (the same device code); last[r] = t.  src [T, D] (a row stride allowed).  The rows
+    must be at step t - 1 (`adam_catch_up`); that is not checked.  Rows the plan does not name are not touched."""
+    what = "adam_apply_rows"
+    ld, n, D, cap = _row_adam_args(what, p, m, v, last, ring)
+    _row_adam_plan(what, plan, n, D, p)
+    T = plan.rows.numel()
+    if not isinstance(src, torch.Tensor) or src.shape != (T, D) or src.dtype != torch.float32 or src.device != p.device \
+            or (D > 1 and src.stride(1) != 1):
+        raise _lib.TagrecError(f"{what}: src must be a float32 tensor [{T}, {D}] with unit inner stride on {p.device}")
+    if t < 1:
+        raise _lib.TagrecError(f"{what}: t={t}: steps are counted from 1")
+    check(load().tagrec_rowadam_apply_f32(plan.workspace, plan.workspace.numel(), T, plan.width, src, src.stride(0) if T > 1 else D,
+                                          p, m, v, ld, n, D, last, ring, cap, int(t), float(betas[0]), float(betas[1]), float(eps),
+                                          stream_ptr()), what)
+
+
+def adam_flush(p, m, v, last, ring, t_floor, t_done, betas=(0.9, 0.999), eps=1e-8):
+    """Every row of the table with last[r] < t_done is replayed to t_done (`adam_catch_up` without a plan); a row that is
+    current costs the read of its `last`.  t_floor: a lower bound of `last` over the whole table."""
+    what = "adam_flush"
+    ld, n, D, cap = _row_adam_args(what, p, m, v, last, ring)
+    _row_adam_window(what, cap, t_floor, t_done)
+    check(load().tagrec_rowadam_flush_f32(p, m, v, ld, n, D, last, ring, cap, int(t_floor), int(t_done), float(betas[0]),
+                                          float(betas[1]), float(eps), stream_ptr()), what)

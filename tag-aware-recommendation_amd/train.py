@@ -152,6 +152,169 @@ class Adam:
                     st["coef"] = torch.zeros(2, dtype=torch.float32, device=p.device)
 
 
+class RowAdam(Adam):
+    """`Adam` whose step on an attached embedding table touches only the rows the batch names -- and still computes what
+    `Adam` computes, bit for bit.  (`torch.optim.SparseAdam` skips the rows without a gradient; dense Adam does not: their
+    m and v decay and p moves along the old m.)  That move is a function of the row's own state and of two per-step
+    scalars, so an unnamed row is left alone and the steps it missed are replayed, in order, the next time something reads
+    it (csrc/rowadam.hip).  No table-sized gradient exists and no pass over the table runs, except the flush below.
+
+        opt = T.RowAdam(model.parameters(), lr=1e-3).attach(model)      # UltraGCN: the one model whose gradient is row-sparse
+        zero_grad() / loss.backward() / step()                          # as before
+
+    A training-mode `model.loss()` catches the batch's rows up, its backward hands (plan, compact gradient) to this
+    optimizer and leaves `table.grad` None, `step()` applies them.  No row is ever more than `max_lag` steps behind: every
+    max_lag steps `step()` runs `flush()`, which brings the whole table to the current step.  The model flushes before
+    anything else reads the table (forward, predict_rating, get_ego_embed, state_dict, eval()).  A caller who reads
+    `model.table.data` directly between steps sees LAGGING rows: call `opt.flush()` first.
+
+    A dense `p.grad` on an attached table (an eval-mode loss, any other graph onto it) is served as `Adam` serves it, after
+    a flush.  Parameters that are not attached behave as in `Adam`.  lr, betas and eps are fixed at construction (the
+    per-step factors are filled ahead); the step number lives on the host, so capturable=True -- and with it
+    `GraphedStep` -- is refused."""
+
+    FILL = 1024                       # steps of the coefficient ring filled per host call, ahead of their use
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_lag=1024, capturable=False):
+        if capturable:
+            raise _lib.TagrecError("RowAdam: capturable=True is not covered -- the step number of the lazy rows lives on the host")
+        from . import rowops
+        if not 1 <= int(max_lag) <= rowops.ADAM_MAX_WINDOW:
+            raise _lib.TagrecError(f"RowAdam: max_lag={max_lag!r} must be 1 .. {rowops.ADAM_MAX_WINDOW}")
+        super().__init__(params, lr, betas, eps, False)
+        self.max_lag = int(max_lag)
+        self._rows = {}                   # id(p) -> the lazy state of an attached table
+        self._frozen = True
+
+    def __setattr__(self, name, value):
+        if name in ("lr", "betas", "eps", "max_lag") and getattr(self, "_frozen", False):
+            raise _lib.TagrecError(f"RowAdam: {name} is fixed after construction (the ring of per-step factors is filled ahead); "
+                                   "build a new optimizer")
+        super().__setattr__(name, value)
+
+    # tagrec_adam_f32 takes lr / b1 / b2 as floats and widens them: the ring is computed from the same values
+    def _f32(self, x):
+        return _lib.ctypes.c_float(x).value
+
+    def attach(self, model):
+        """Make `model`'s training step row-sparse under this optimizer (`model.set_row_optimizer`).  Only a model whose
+        step names the rows it changes has the hook: UltraGCN."""
+        if not hasattr(model, "set_row_optimizer"):
+            raise _lib.TagrecError(f"RowAdam.attach: {type(model).__name__} is not covered -- its gradients are dense (propagation "
+                                   "spreads every batch row's gradient over the table); only UltraGCN's step names its rows")
+        table = model.table
+        if not any(q is table for q in self.params):
+            raise _lib.TagrecError("RowAdam.attach: the model's table is not one of this optimizer's parameters")
+        _lib.require_gpu_tensor(table.data, torch.float32, "RowAdam.attach: the table")
+        if id(table) not in self._rows:
+            st = self.state.get(id(table))
+            if st is None:
+                st = self.state[id(table)] = {"m": torch.zeros_like(table.data), "v": torch.zeros_like(table.data), "t": 0}
+            cap = self.FILL * ((self.max_lag + 1 + 2 * self.FILL - 1) // self.FILL)        # >= max_lag + 1 + one block ahead
+            self._rows[id(table)] = {"p": table, "last": torch.full((table.shape[0],), st["t"], dtype=torch.int32, device=table.device),
+                                     "ring": torch.zeros(cap, 2, dtype=torch.float32, device=table.device), "filled": st["t"],
+                                     "flushed": st["t"], "pending": None}
+            self._fill(self._rows[id(table)], st["t"] + 1)
+        table._tagrec_owner = self
+        model.set_row_optimizer(self)
+        return self
+
+    def _fill(self, rs, t):
+        """The ring holds the factors of every step up to t: filled a block ahead, FILL-aligned so that a block never wraps.
+        One host-to-device copy per block, none per step."""
+        from . import rowops
+        cap = rs["ring"].shape[0]
+        while rs["filled"] < t:
+            t0 = rs["filled"] + 1
+            n = self.FILL - t0 % self.FILL                      # up to the next multiple of FILL (exclusive)
+            coef = rowops.adam_coef(self._f32(self.lr), self._f32(self.betas[0]), self._f32(self.betas[1]), t0, n)
+            rs["ring"][t0 % cap:t0 % cap + n].copy_(coef)
+            rs["filled"] = t0 + n - 1
+
+    def lagging_rows(self, p):
+        """Number of rows of the attached table `p` that are behind the optimizer's step -- reads the device (tests, tools)."""
+        rs = self._rows[id(p)]
+        return int((rs["last"] < self.state[id(p)]["t"]).sum())
+
+    def row_state(self, p):
+        """(m, v, last, step) of an attached table."""
+        st = self.state[id(p)]
+        return st["m"], st["v"], self._rows[id(p)]["last"], st["t"]
+
+    def catch_up(self, p, plan):
+        """Bring the rows of `plan` to the steps done so far (the forward pass of the model's loss, before it gathers them)."""
+        from . import rowops
+        rs, st = self._rows[id(p)], self.state[id(p)]
+        rowops.adam_catch_up(plan, p.data, st["m"], st["v"], rs["last"], rs["ring"], rs["flushed"], st["t"], self.betas, self.eps)
+
+    def row_grad(self, p, plan, grad):
+        """The model's backward: the compact gradient of `plan`'s rows, applied by the next step()."""
+        rs = self._rows[id(p)]
+        if rs["pending"] is not None:
+            raise _lib.TagrecError("RowAdam: a second backward() before step() on a row-sparse step")
+        rs["pending"] = (plan, grad)
+
+    def zero_grad(self, set_to_none=True):
+        super().zero_grad(set_to_none)
+        for rs in self._rows.values():       # a gradient that was never stepped on is dropped, as p.grad would be
+            rs["pending"] = None
+
+    @torch.no_grad()
+    def flush(self):
+        """Bring every row of every attached table to the optimizer's step.  Idempotent; one pass over `last`, and over
+        the rows that lag."""
+        from . import rowops
+        for rs in self._rows.values():
+            st = self.state[id(rs["p"])]
+            if rs["flushed"] < st["t"]:
+                rowops.adam_flush(rs["p"].data, st["m"], st["v"], rs["last"], rs["ring"], rs["flushed"], st["t"], self.betas, self.eps)
+                rs["flushed"] = st["t"]
+
+    @torch.no_grad()
+    def step(self):
+        from . import rowops
+        dense, lazy = [], []
+        for rs in self._rows.values():
+            p, st = rs["p"], self.state[id(rs["p"])]
+            if rs["pending"] is not None:
+                if p.grad is not None:
+                    raise _lib.TagrecError("RowAdam: the table received a row-sparse gradient and a gradient tensor in one step")
+                lazy.append((rs, st))
+            elif p.grad is not None:             # a dense gradient: Adam's own pass over a table that is current
+                dense.append((rs, st))
+        if dense:
+            self.flush()
+        for rs, st in lazy:
+            plan, grad = rs["pending"]
+            self._fill(rs, st["t"] + 1)
+            rowops.adam_apply_rows(plan, grad, rs["p"].data, st["m"], st["v"], rs["last"], rs["ring"], st["t"] + 1, self.betas, self.eps)
+            rs["pending"] = None
+            st["t"] += 1
+        super().step()                           # every parameter with a gradient tensor, the dense tables among them
+        for rs, st in dense:
+            rs["last"].fill_(st["t"])
+            rs["flushed"] = st["t"]
+            self._fill(rs, st["t"] + 1)
+        for rs, st in lazy:
+            if st["t"] - rs["flushed"] >= self.max_lag:
+                self.flush()
+            self._fill(rs, st["t"] + 1)
+
+
+def row_optimizer(model):
+    """The `RowAdam` attached to `model` (`RowAdam.attach`), or None.  Live only while it is still the newest optimizer built
+    over the table: one created later revokes it -- the table is flushed first, so that the new owner starts from the dense
+    optimizer's state."""
+    opt = getattr(model, "_row_opt", None)
+    if opt is None:
+        return None
+    if getattr(model.table, "_tagrec_owner", None) is not opt:
+        opt.flush()
+        model._row_opt = None
+        return None
+    return opt
+
+
 def _fused_tables(model):
     """The parameters a model can update inside its own backward pass: `model.fused_tables()` (TGCN: the three node
     tables) or the single `model.table`."""

@@ -14,7 +14,12 @@ construction from the train edges.  The terms are MEANS over the batch where the
 batch's rows (user, positive, negatives), not on the whole tables.  ug_neighbors = 0 turns the neighbour term off.
 
 Nothing in loss() reads the host.  deterministic=True folds the compact gradients through `help.ultragcn_plans` (the same bits
-every run).  `Adam.fuse_into` is refused: there is no backward product whose epilogue could take the update."""
+every run).  `Adam.fuse_into` is refused: there is no backward product whose epilogue could take the update.
+
+`RowAdam.attach(model)` (train.py) makes the step row-sparse: a training-mode loss() catches the batch's rows up to the
+optimizer's step and its backward hands the optimizer (plan, compact gradient) instead of a table-sized gradient.  Rows a
+batch did not name then LAG behind the dense optimizer until they are next read; forward(), predict_rating(), get_ego_embed(),
+state_dict() and eval() flush them first.  `model.table.data` read directly between steps is not flushed."""
 import numpy as np
 import torch
 
@@ -60,8 +65,47 @@ class UltraGCN(TableModel):
             raise _lib.TagrecError("UltraGCN: Adam.fuse_into is not covered -- the step has no backward product whose epilogue "
                                    "could apply the update")
 
+    def set_row_optimizer(self, opt):
+        """`RowAdam.attach(model)`: a training-mode loss() catches the batch's rows up to the optimizer's step, and its
+        backward hands the optimizer (plan, compact gradient) in place of a table-sized gradient.  Between steps the rows a
+        batch did not name LAG behind the dense optimizer; every reader below flushes them first.  None switches it off."""
+        old = getattr(self, "_row_opt", None)
+        if old is not None and old is not opt:
+            old.flush()
+        self._row_opt = opt
+
+    def _row_optimizer(self):
+        from .train import row_optimizer
+        return row_optimizer(self)
+
+    def _flush_rows(self):
+        opt = self._row_optimizer()
+        if opt is not None:
+            opt.flush()
+        return opt
+
     def forward(self):
+        self._flush_rows()
         return tuple(self.embed)
+
+    def get_ego_embed(self):
+        self._flush_rows()
+        return self.embed
+
+    get_ego_emb = get_ego_embed
+
+    def predict_rating(self, users):
+        self._flush_rows()
+        return super().predict_rating(users)
+
+    def state_dict(self, *args, **kwargs):
+        self._flush_rows()
+        return super().state_dict(*args, **kwargs)
+
+    def train(self, mode=True):
+        if not mode:
+            self._flush_rows()
+        return super().train(mode)
 
     def loss(self, batch_data):
         batch = batch_data.to(self.device, torch.int64).contiguous()
@@ -70,8 +114,12 @@ class UltraGCN(TableModel):
             raise _lib.TagrecError(f"{name}: a batch of shape {tuple(batch.shape)} does not fit n_negatives={self.n_negatives} "
                                    f"(expected [B, {2 + self.n_negatives}] = user, positive, {self.n_negatives} negative(s))")
         nu, ni = self.num_list
-        U, I = self.embed
         stage = S.Ultra(self.tables)         # one per step: the plans and the loss share its slot ids
+        opt = self._flush_rows() if not self.training else self._row_optimizer()
+        if opt is not None and self.training:            # row-sparse step: ONE plan over the stage's rows, no table gradient
+            mul, l2 = H.ultragcn_row_loss(self.table, nu, batch, self.tables, opt, stage)
+            return mul, self.reg * l2
+        U, I = self.embed
         plans = H.ultragcn_plans(batch, self.tables, nu, ni, self.dim_latent, stage) if self.deterministic else None
         mul, l2 = H.ultragcn_loss(U, I, U, I, batch, self.tables, plans, stage)
         return mul, self.reg * l2
